@@ -17,7 +17,14 @@ Multi-GPU (torchrun): every rank owns its own config-2 shard (per-contig shardin
 independent; weak scaling) and the only collective is the int64 totals all-reduce over RCCL of
 each step, overlapped with the next step's kernels (double-buffered).
 
-Prints one JSON line (rank 0). ``roofline`` is for the whole step (the prep kernels and the
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON line (rank 0) with the
+headline figure (``value`` in reads/s, ``ms_per_step``). ``--dump-outputs DIR`` also writes what the
+last timed step computed as ``DIR/<name>.npy`` (dump_outputs; the inputs are seeded: the same
+arguments give the same files). Everything else is measured with ``--full`` only: the end-to-end,
+side-config and BAM-walk child runs, the comparison timings, the per-kernel durations and roofline,
+the PCIe-inclusive and FASTQ lines, the speculative-plan check and the CPU baseline.
+
+With ``--full``, ``roofline`` is for the whole step (the prep kernels and the
 masking kernels, all of which a step needs): the algorithmic bytes of the batch (SURVEY §8(d):
 per read ceil(L/2) in + ceil(L/2) out + 4 n_cigar + 16, per extra incidence ceil(L/2) + 4 n_cigar +
 8, per scope ceil(span/2) of reference) over the summed average durations of the step's kernels,
@@ -198,6 +205,56 @@ def make_batch(args, rank: int, k: int = 0):
     idp = {"germline_del_per_kb": 0.1, "seq_indel_per_base": 1.5e-4} if args.config == "c2id" else {}
     return config2_batch(n_reads=batch_reads(args, k), genome=args.genome, n_windows=args.windows,
                          n_germline=args.germline, seed=seed, read_seed=rs, **idp)
+
+
+def make_batches(args, rank: int, n: int) -> list:
+    """Batches 0 .. n-1 of this rank (make_batch), the arrays the same as made one after another. The
+    first is made alone: it generates the sample's genome and sites, which the others share. The
+    others are made beside each other on threads (numpy releases the GIL in the sorts, gathers and
+    random draws that take the time), in less than half the time of making them in turn."""
+    from concurrent.futures import ThreadPoolExecutor
+    out = [make_batch(args, rank, 0)]
+    if n > 1:
+        with ThreadPoolExecutor(min(n - 1, 5)) as ex:
+            out += list(ex.map(lambda k: make_batch(args, rank, k), range(1, n)))
+    return out
+
+
+DUMP_BYTES = 12 << 20   # of one dumped array; four or five arrays per dump
+
+
+def _dump_sample(a: np.ndarray, dtype) -> np.ndarray:
+    """``a`` as ``dtype``; an array of more than DUMP_BYTES the rows at a fixed set of indices (drawn
+    with seed 0 for the array's length, sorted: the same rows in every run over the same inputs)."""
+    a = np.asarray(a)
+    row = np.dtype(dtype).itemsize * int(np.prod(a.shape[1:], dtype=np.int64))
+    keep = DUMP_BYTES // max(1, row)
+    if len(a) > keep:
+        a = a[np.unique(np.random.default_rng(0).integers(0, len(a), keep))]
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def dump_outputs(out_dir: str, db, ind) -> dict:
+    """--dump-outputs: what a caller of the timed path receives for the batch of the last timed step
+    (ganon_batch_download: the masked bases, the masked calls and masked bases per scope, the
+    totals; the records of the germline indel tally where the step runs it), one DIR/<name>.npy
+    each, float32 or float64 (every value is an integer either holds exactly). Long outputs are
+    written as fixed samples (_dump_sample). Returns name -> [dumped rows, rows of the output]."""
+    os.makedirs(out_dir, exist_ok=True)
+    seq, calls, bases, tot = db.download()
+    outs = {"masked_seq_nt16": (seq, np.float32), "scope_masked_calls": (calls, np.float64),
+            "scope_masked_bases": (bases, np.float64), "totals": (tot, np.float64)}
+    if ind is not None:
+        recs = ind.download()
+        cols = np.stack([recs[f].astype(np.float64) for f in recs.dtype.names], axis=1) if len(recs) \
+            else np.zeros((0, len(recs.dtype.names)))
+        outs["indel_records"] = (cols, np.float64)
+    written = {}
+    for name, (a, dt) in outs.items():
+        s = _dump_sample(a, dt)
+        np.save(os.path.join(out_dir, name + ".npy"), s)
+        written[name] = [len(s), len(a)]
+    return written
 
 
 def fastq_bench(masker, db, arr, args, torch, rank: int) -> dict:
@@ -541,7 +598,7 @@ def side_config_lines(args) -> dict:
     out = {}
     for name, extra in SIDE_CONFIGS.items():
         stage(f"side config {name} (child bench run)")
-        r = _child_json([sys.executable, os.path.abspath(__file__), "--config", name, "--no-e2e", "--no-pcie",
+        r = _child_json([sys.executable, os.path.abspath(__file__), "--config", name, "--full", "--no-e2e", "--no-pcie",
                          "--no-fastq", "--no-cpu-baseline", "--no-side-configs"] + extra, {}, 600)
         if "error" in r:
             out[name] = {"error": r["error"]}
@@ -629,6 +686,52 @@ def pmc_summary(config: str, reads: int, explicit: str = None, kind: str = "mask
     return None, None, note
 
 
+def step_figures(args, prof_arrs, arr, ktimes: dict, indel_info: dict) -> dict:
+    """The per-kernel fields of a --full line (roofline, pass, the indel tally's ms per step) from the
+    profiled steps' kernel durations ``ktimes`` (name -> [launches, ms]) over context 0's batches
+    ``prof_arrs``."""
+    from genomeanonymizer_amd.synth.batch import algorithmic_bytes
+    # algorithmic bytes of the profiled steps: context 0's batches, one step each in turn
+    kbs = [kernel_bytes(a) for a in prof_arrs]
+    kb = {k: sum(x[k] for x in kbs) // len(kbs) for k in kbs[0]}
+    kb.update(indel_bytes(arr, indel_info["observations"], indel_info["emitted"]))
+    per_kernel = {n: {"launches": c, "avg_ms": ms / c} for n, (c, ms) in ktimes.items()}
+    # the dominant kernel: the longest one the algorithmic bytes are counted for (the group kernel;
+    # a prep kernel can take longer on long reads, but it has no byte count of its own)
+    counted = [n for n in per_kernel if kb.get(kernel_class(n))] or list(per_kernel)
+    dom = max(counted, key=lambda n: per_kernel[n]["avg_ms"] * per_kernel[n]["launches"])
+    indel_ms = sum(v["avg_ms"] * v["launches"] for n, v in per_kernel.items() if "indel" in n) / args.steps
+    dom_bytes = kb.get(kernel_class(dom), 0)
+    dom_ms = per_kernel[dom]["avg_ms"]
+    pass_ms = sum(v["avg_ms"] * v["launches"] for v in per_kernel.values()) / args.steps
+    alg_total = sum(algorithmic_bytes(a) for a in prof_arrs) // len(prof_arrs)
+    achieved = alg_total / (pass_ms * 1e-3) / 1e9
+    traffic = dom_traffic = None
+    # the newest PMC summary of this config and size taken on these kernel sources (tools/pmc_step.py)
+    pmc, pmc_used, pmc_note = pmc_summary(args.config, args.reads, args.pmc)
+    if pmc is not None:
+        traffic = pmc.get("step_hbm_bytes")
+        dom_traffic = pmc.get("kernels", {}).get("k_group", {}).get("hbm_bytes_per_launch")
+    return {
+        "roofline": {"bound": "hbm", "kernel": "step: " + " + ".join(per_kernel), "achieved": round(achieved, 1),
+                     "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                     "traffic": traffic, "traffic_source": pmc_used, "traffic_note": pmc_note,
+                     "algorithmic_bytes_per_launch": alg_total,
+                     "avg_launch_ms": round(pass_ms, 5),
+                     "dominant": {"kernel": dom, "algorithmic_bytes_per_launch": dom_bytes,
+                                  "avg_launch_ms": round(dom_ms, 5),
+                                  "achieved": round(dom_bytes / (dom_ms * 1e-3) / 1e9, 1),
+                                  "traffic": dom_traffic if "k_group" in dom else None,
+                                  "frac": round(dom_bytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}},
+        "pass": {"kernel_ms": round(pass_ms, 4), "algorithmic_bytes": alg_total,
+                 "prep_ms": round(sum(v["avg_ms"] * v["launches"] for n, v in per_kernel.items()
+                                      if n in PREP_KERNELS) / args.steps, 4),
+                 "kernels": {n: {"avg_ms": round(v["avg_ms"], 5), "launches_per_step": v["launches"] // args.steps,
+                                 "alg_bytes": kb.get(kernel_class(n))} for n, v in per_kernel.items()}},
+        "indel_ms": round(indel_ms, 4),
+    }
+
+
 _STAGE = ["start", time.time()]
 
 
@@ -656,6 +759,13 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the end-to-end, side-config and BAM-walk child runs, "
+                         "the comparison timings, per-kernel durations and roofline, PCIe-inclusive and FASTQ lines, the "
+                         "speculative-plan check and the CPU baseline (each still has its own --no-... switch). Without "
+                         "it the run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (dump_outputs) as DIR/<name>.npy")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2",
                     help="c2 = BASELINE configs[1] (the metric's workload); c3 / c5 = SURVEY §8(d) density and "
                          "long-read shapes, for their own lines")
@@ -716,6 +826,11 @@ def main() -> None:
             setattr(args, k, v)
     if args.config == "c5" or args.resident:
         args.batches = 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run: the headline figure alone
+        args.no_e2e = args.no_side_configs = args.no_bam_decode = True
+        args.no_pcie = args.no_fastq = args.no_cpu_baseline = True
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -731,6 +846,11 @@ def main() -> None:
         stage("device BAM record walk (child run)")
         bam_decode = _child_json([sys.executable, os.path.join(REPO, "tools", "bam_cols_bench.py")], {}, 600)
     stage(f"{args.config}: generating {args.pipeline * args.batches} batches")
+    # (on a thread: torch is imported and the device opened while numpy generates)
+    from concurrent.futures import ThreadPoolExecutor
+    t_gen = time.perf_counter()
+    gen_pool = ThreadPoolExecutor(1)
+    gen = gen_pool.submit(make_batches, args, rank, args.pipeline * args.batches)
     import torch
     local = int(os.environ.get("LOCAL_RANK", 0))
     dev = local % max(1, torch.cuda.device_count())   # == local on a node with a GPU per rank
@@ -754,8 +874,8 @@ def main() -> None:
     # new batch arriving), and a context's plan (latency-bound scan and emit) runs beside another
     # context's group kernel (bandwidth-bound)
     n_b = args.pipeline * args.batches
-    t_gen = time.perf_counter()
-    batches = [make_batch(args, rank, k) for k in range(n_b)]
+    batches = gen.result()
+    gen_pool.shutdown()
     t_gen = time.perf_counter() - t_gen
     arr, info = batches[0]
     t_up = time.perf_counter()
@@ -857,10 +977,15 @@ def main() -> None:
     if dist is not None:
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
     dt = float(dt_t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        stage("writing the last timed step's outputs")
+        sl, b = pick(args.steps - 1)
+        dumped = dump_outputs(args.dump_outputs, sl["dbs"][b], sl["inds"][b])
 
     # the same steps on one context and one stream (its batches in turn, no overlap), for comparison
     one_stream_ms = None
-    if len(slots) > 1:
+    if args.full and len(slots) > 1:
         torch.cuda.synchronize()
         t = time.perf_counter()
         for i in range(args.steps):
@@ -871,7 +996,7 @@ def main() -> None:
     # the same pipelined steps with every plan synchronous (GANON_PARAM_SPEC_PLAN 0: the host waits
     # for each scan before it launches the run), for comparison
     sync_ms = None
-    if not args.resident and args.spec_plan:
+    if args.full and not args.resident and args.spec_plan:
         for sl in slots:
             sl["m"].set_param(native.PARAM_SPEC_PLAN, 0)
         torch.cuda.synchronize()
@@ -886,9 +1011,9 @@ def main() -> None:
 
     # per-kernel durations: context 0's steps again (its batches in turn) with a HIP event pair
     # around each launch
-    masker.set_profiling(True)
+    masker.set_profiling(args.full)
     ktimes: dict = {}
-    for i in range(args.steps):
+    for i in range(args.steps if args.full else 0):
         b = i % args.batches
         db_i, ind_i = slots[0]["dbs"][b], slots[0]["inds"][b]
         if not args.resident:
@@ -902,12 +1027,13 @@ def main() -> None:
             k[0] += launches
             k[1] += ms
     masker.set_profiling(False)
-    stage("pcie / fastq / cpu baseline")
+    if args.full:
+        stage("pcie / fastq / cpu baseline")
     pcie = None if args.no_pcie else pcie_bench(masker, db, arr, args, torch)
     fastq = None if args.no_fastq else fastq_bench(masker, db, arr, args, torch, rank)
     # the run-only step of round 2 (plan kept from the previous step), for comparison
     run_only_ms = None
-    if not args.resident:
+    if args.full and not args.resident:
         db.replan()
         torch.cuda.synchronize()
         t = time.perf_counter()
@@ -917,8 +1043,12 @@ def main() -> None:
         run_only_ms = (time.perf_counter() - t) / args.steps * 1e3
     totals = db.totals()     # (also reports any check the runs made: a bad batch raises here)
     batch_info = db.info()
+    if not args.full:   # (the full run's per-batch check below reads every batch's)
+        for sl in slots:
+            for d in sl["dbs"]:
+                d.totals()
     if ind is not None:
-        irecs = ind.download()
+        irecs = ind.download() if args.full else np.zeros(0, native.INDEL_REC)
         indel_info = ind.info()
         ind.free()
     else:
@@ -937,7 +1067,7 @@ def main() -> None:
         job_totals = totals
     # every batch's last (speculative) result equals a full synchronous plan + run of it
     per_batch = []
-    for sl in slots:
+    for sl in slots if args.full else ():
         spec_tots = []
         for rnd in range(2):    # (round 0 leaves every batch planned after another: round 1 is a new-batch plan)
             spec_tots = []
@@ -967,28 +1097,8 @@ def main() -> None:
     db.free()
     ref.free()
 
-    # algorithmic bytes of the profiled steps: context 0's batches, one step each in turn
-    prof_arrs = slots[0]["arrs"]
-    kbs = [kernel_bytes(a) for a in prof_arrs]
-    kb = {k: sum(x[k] for x in kbs) // len(kbs) for k in kbs[0]}
-    kb.update(indel_bytes(arr, indel_info["observations"], indel_info["emitted"]))
-    per_kernel = {n: {"launches": c, "avg_ms": ms / c} for n, (c, ms) in ktimes.items()}
-    # the dominant kernel: the longest one the algorithmic bytes are counted for (the group kernel;
-    # a prep kernel can take longer on long reads, but it has no byte count of its own)
-    counted = [n for n in per_kernel if kb.get(kernel_class(n))] or list(per_kernel)
-    dom = max(counted, key=lambda n: per_kernel[n]["avg_ms"] * per_kernel[n]["launches"])
-    indel_ms = sum(v["avg_ms"] * v["launches"] for n, v in per_kernel.items() if "indel" in n) / args.steps
-    dom_bytes = kb.get(kernel_class(dom), 0)
-    dom_ms = per_kernel[dom]["avg_ms"]
-    pass_ms = sum(v["avg_ms"] * v["launches"] for v in per_kernel.values()) / args.steps
-    alg_total = sum(algorithmic_bytes(a) for a in prof_arrs) // len(prof_arrs)
-    achieved = alg_total / (pass_ms * 1e-3) / 1e9
-    traffic = dom_traffic = None
-    # the newest PMC summary of this config and size taken on these kernel sources (tools/pmc_step.py)
-    pmc, pmc_used, pmc_note = pmc_summary(args.config, args.reads, args.pmc)
-    if pmc is not None:
-        traffic = pmc.get("step_hbm_bytes")
-        dom_traffic = pmc.get("kernels", {}).get("k_group", {}).get("hbm_bytes_per_launch")
+    # the per-kernel figures of the profiled steps: context 0's batches, one step each in turn
+    fig = step_figures(args, slots[0]["arrs"], arr, ktimes, indel_info) if args.full else {}
 
     reads_total = reads_timed * world
     value = reads_total / dt
@@ -1015,16 +1125,7 @@ def main() -> None:
                    "window_scopes": info.get("window_scopes"), "union_scopes": info.get("union_scopes"),
                    "passthrough_reads": info.get("passthrough_reads"), "parallelism": f"contig-shard x{world}",
                    "pipeline": args.pipeline},
-        "roofline": {"bound": "hbm", "kernel": "step: " + " + ".join(per_kernel), "achieved": round(achieved, 1),
-                     "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                     "traffic": traffic, "traffic_source": pmc_used, "traffic_note": pmc_note,
-                     "algorithmic_bytes_per_launch": alg_total,
-                     "avg_launch_ms": round(pass_ms, 5),
-                     "dominant": {"kernel": dom, "algorithmic_bytes_per_launch": dom_bytes,
-                                  "avg_launch_ms": round(dom_ms, 5),
-                                  "achieved": round(dom_bytes / (dom_ms * 1e-3) / 1e9, 1),
-                                  "traffic": dom_traffic if "k_group" in dom else None,
-                                  "frac": round(dom_bytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}},
+        "roofline": fig.get("roofline"),
         "step_kind": ("DIAGNOSTIC: the indel tally left out; " if not args.indel_tally else "") +
                      ("resident batch, plan kept (run only)" if args.resident else
                      (f"fresh batch: device plan (replan: validation scan, group table, shape checks) + run every "
@@ -1041,16 +1142,12 @@ def main() -> None:
         "run_only_ms_per_step": round(run_only_ms, 4) if run_only_ms else None,
         "one_stream_ms_per_step": round(one_stream_ms, 4) if one_stream_ms else None,
         "batch_shape": shape,
-        "pass": {"kernel_ms": round(pass_ms, 4), "algorithmic_bytes": alg_total,
-                 "prep_ms": round(sum(v["avg_ms"] * v["launches"] for n, v in per_kernel.items()
-                                      if n in PREP_KERNELS) / args.steps, 4),
-                 "kernels": {n: {"avg_ms": round(v["avg_ms"], 5), "launches_per_step": v["launches"] // args.steps,
-                                 "alg_bytes": kb.get(kernel_class(n))} for n, v in per_kernel.items()}},
+        "pass": fig.get("pass"),
         "indel": {"observations": indel_info["observations"], "emitted": indel_info["emitted"],
                   "incidences": indel_info["incidences"],
-                  "masked_calls": int((irecs["kind"] == native.INDEL_CALL).sum()),
-                  "support_records": int((irecs["kind"] == native.INDEL_SUPPORT).sum()),
-                  "ms_per_step": round(indel_ms, 4)},
+                  "masked_calls": int((irecs["kind"] == native.INDEL_CALL).sum()) if args.full else None,
+                  "support_records": int((irecs["kind"] == native.INDEL_SUPPORT).sum()) if args.full else None,
+                  "ms_per_step": fig.get("indel_ms")},
         "e2e": e2e.get("e2e"),
         "side_configs": side,
         "bam_decode": bam_decode,
@@ -1059,6 +1156,8 @@ def main() -> None:
         "totals": {k: int(v) for k, v in zip(native.TOTAL_NAMES, job_totals)},
         "batch": batch_info,
         "setup_s": {"generate": round(t_gen, 1), "upload_pcie": round(t_up, 2)},
+        "full": args.full,
+        "dumped_outputs": dumped,
     }
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(arr, info["reads"])

@@ -105,7 +105,7 @@ def main():
         rank = dist.get_rank()
         os.environ.setdefault("GANON_DEVICE", str(int(os.environ.get("LOCAL_RANK", 0)) % max(1, torch.cuda.device_count())))
     d = sys.argv[1]
-    out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(REPO, "gpurun_out", "e2e")
+    out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(REPO, "bench_out", "e2e")
     os.makedirs(out, exist_ok=True)
     from genomeanonymizer_amd import short_read_tumor_normal_anonymizer as sr
     from genomeanonymizer_amd.io.fasta import FastaRef

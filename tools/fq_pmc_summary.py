@@ -11,7 +11,7 @@ from collections import defaultdict
 tag = sys.argv[1]
 subs = sys.argv[2:] or ["k_fq_format", "k_fq_off", "k_fq_bsum"]
 res = defaultdict(dict)
-for d in sorted(glob.glob(f"gpurun_out/fqpmc_{tag}_*")):
+for d in sorted(glob.glob(f"bench_out/fqpmc_{tag}_*")):
     if not os.path.isdir(d):
         continue
     counter = d.split(f"fqpmc_{tag}_", 1)[1]

@@ -6,19 +6,19 @@
 # Each step has its own time limit; the chain stops at the first failure.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out/ichk
+mkdir -p bench_out/ichk
 export GANON_HIP_LIB=genomeanonymizer_amd/variants/libganon_hip_ichk.so
 A="--steps 5 --warmup 2 --no-cpu-baseline --no-pcie --no-fastq --no-e2e --no-side-configs"
 timeout -k 10 600 python -u -m pytest tests/test_indels.py -m gpu -v --timeout 300 --timeout-method thread \
-  > gpurun_out/ichk/indel_tests.log 2>&1 || { tail -40 gpurun_out/ichk/indel_tests.log; exit 1; }
-grep -E "passed|failed" gpurun_out/ichk/indel_tests.log | tail -1
+  > bench_out/ichk/indel_tests.log 2>&1 || { tail -40 bench_out/ichk/indel_tests.log; exit 1; }
+grep -E "passed|failed" bench_out/ichk/indel_tests.log | tail -1
 for mode in default global; do
   if [ $mode = global ]; then export GANON_INDEL_SORTMODE=global; fi
   timeout -k 10 600 python -u -m pytest tests/test_gpu.py::test_hip_config2_indel_cigars_full_size_matches_oracle -m gpu -v \
-    --timeout 500 --timeout-method thread > gpurun_out/ichk/c2id_full_$mode.log 2>&1 || { tail -40 gpurun_out/ichk/c2id_full_$mode.log; exit 1; }
-  echo "c2id full-size ($mode): $(grep -E 'passed|failed' gpurun_out/ichk/c2id_full_$mode.log | tail -1)"
+    --timeout 500 --timeout-method thread > bench_out/ichk/c2id_full_$mode.log 2>&1 || { tail -40 bench_out/ichk/c2id_full_$mode.log; exit 1; }
+  echo "c2id full-size ($mode): $(grep -E 'passed|failed' bench_out/ichk/c2id_full_$mode.log | tail -1)"
 done
 unset GANON_INDEL_SORTMODE
-timeout -k 10 300 python bench.py --config c2id $A > gpurun_out/ichk/c2id.json 2> gpurun_out/ichk/c2id.err || { tail -20 gpurun_out/ichk/c2id.err; exit 1; }
-timeout -k 10 300 python bench.py --config c5 --reads 10000 --genome 100000000 $A > gpurun_out/ichk/c5.json 2> gpurun_out/ichk/c5.err || { tail -20 gpurun_out/ichk/c5.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config c2id $A > bench_out/ichk/c2id.json 2> bench_out/ichk/c2id.err || { tail -20 bench_out/ichk/c2id.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config c5 --reads 10000 --genome 100000000 $A > bench_out/ichk/c5.json 2> bench_out/ichk/c5.err || { tail -20 bench_out/ichk/c5.err; exit 1; }
 echo "exit=0"

@@ -8,11 +8,11 @@ set -o pipefail
 REPO="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd /tmp && export TMPDIR=/tmp
 cd "$REPO"
-mkdir -p gpurun_out
+mkdir -p bench_out
 TAG=${TAG:-fq}
 ARGS="--reads ${READS:-9800000} --runs 3"   # (the bench formats its first batch: 9.8 M records)
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv -- \
-    python3 tools/fq_run.py $ARGS > gpurun_out/fqrun_$TAG.json 2> gpurun_out/prof_$TAG.err || exit $?
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d bench_out/prof_$TAG -o run --output-format csv -- \
+    python3 tools/fq_run.py $ARGS > bench_out/fqrun_$TAG.json 2> bench_out/prof_$TAG.err || exit $?
 echo "trace done"
 P1="TCC_EA0_RDREQ_32B TCC_EA0_RDREQ_64B TCC_EA0_RDREQ_128B TCC_EA0_WRREQ"
 P2="TCC_EA0_WRREQ_64B FETCH_SIZE"
@@ -20,8 +20,8 @@ P3="WRITE_SIZE"
 i=0
 for P in "$P1" "$P2" "$P3"; do
   i=$((i + 1))
-  timeout -k 10 -s KILL 300 rocprofv3 --pmc $P -d gpurun_out/pmc_${TAG}_p$i -o run --output-format csv -- \
-      python3 tools/fq_run.py $ARGS > /dev/null 2> gpurun_out/pmc_${TAG}_p$i.err || exit $?
+  timeout -k 10 -s KILL 300 rocprofv3 --pmc $P -d bench_out/pmc_${TAG}_p$i -o run --output-format csv -- \
+      python3 tools/fq_run.py $ARGS > /dev/null 2> bench_out/pmc_${TAG}_p$i.err || exit $?
   echo "pmc pass $i done"
 done
 echo "exit=0"

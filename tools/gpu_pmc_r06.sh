@@ -8,15 +8,15 @@ A="--no-e2e --no-side-configs --no-fastq --no-pcie"
 R=${ROUND_TAG:-r06}
 for c in ${CONFIGS:-fastq c3 c5 c2 c2id}; do
   case $c in
-    fastq) TAG=${R}fq bash tools/gpu_pmc_fastq.sh && python3 tools/pmc_step.py ${R}fq fastq 9800000 gpurun_out/pmc_fastq.json || exit 1 ;;
+    fastq) TAG=${R}fq bash tools/gpu_pmc_fastq.sh && python3 tools/pmc_step.py ${R}fq fastq 9800000 bench_out/pmc_fastq.json || exit 1 ;;
     c3) TAG=${R}c3 BENCH_ARGS="--config c3 --reads 10000000 --genome 25000000 --windows 2500 --germline 25000 $A" bash tools/gpu_pmc_step.sh \
-          && python3 tools/pmc_step.py ${R}c3 c3 10000000 gpurun_out/pmc_step_c3.json || exit 1 ;;
+          && python3 tools/pmc_step.py ${R}c3 c3 10000000 bench_out/pmc_step_c3.json || exit 1 ;;
     c5) TAG=${R}c5 BENCH_ARGS="--config c5 --reads 10000 --genome 100000000 $A" bash tools/gpu_pmc_step.sh \
-          && python3 tools/pmc_step.py ${R}c5 c5 10000 gpurun_out/pmc_step_c5.json || exit 1 ;;
+          && python3 tools/pmc_step.py ${R}c5 c5 10000 bench_out/pmc_step_c5.json || exit 1 ;;
     c2) TAG=${R}c2 BENCH_ARGS="$A" bash tools/gpu_pmc_step.sh \
-          && python3 tools/pmc_step.py ${R}c2 c2 10000000 gpurun_out/pmc_step_c2.json || exit 1 ;;
+          && python3 tools/pmc_step.py ${R}c2 c2 10000000 bench_out/pmc_step_c2.json || exit 1 ;;
     c2id) TAG=${R}c2id BENCH_ARGS="--config c2id $A" bash tools/gpu_pmc_step.sh \
-          && python3 tools/pmc_step.py ${R}c2id c2id 10000000 gpurun_out/pmc_step_c2id.json || exit 1 ;;
+          && python3 tools/pmc_step.py ${R}c2id c2id 10000000 bench_out/pmc_step_c2id.json || exit 1 ;;
   esac
   echo "== $c done"
 done

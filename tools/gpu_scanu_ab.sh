@@ -4,7 +4,7 @@
 # own time limit; the chain stops at the first failure.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out/scanu_ab
+mkdir -p bench_out/scanu_ab
 A="--steps ${STEPS:-50} --warmup 5 --no-cpu-baseline --no-pcie --no-fastq --no-e2e --no-side-configs"
 V=genomeanonymizer_amd/variants
 for rep in 1 2; do
@@ -12,12 +12,12 @@ for rep in 1 2; do
     for cfg in c2 c2id; do
       case $cfg in c2id) X="--config c2id" ;; *) X="" ;; esac
       if [ "$u" = 4 ]; then LIB=""; else LIB="$V/libganon_hip_su$u.so"; fi
-      GANON_HIP_LIB=$LIB timeout -k 10 300 python bench.py $A $X > gpurun_out/scanu_ab/${cfg}_u${u}_$rep.json \
-        2> gpurun_out/scanu_ab/${cfg}_u${u}_$rep.err || { tail -20 gpurun_out/scanu_ab/${cfg}_u${u}_$rep.err; exit 1; }
+      GANON_HIP_LIB=$LIB timeout -k 10 300 python bench.py --full $A $X > bench_out/scanu_ab/${cfg}_u${u}_$rep.json \
+        2> bench_out/scanu_ab/${cfg}_u${u}_$rep.err || { tail -20 bench_out/scanu_ab/${cfg}_u${u}_$rep.err; exit 1; }
       python3 - "$cfg" "$u" "$rep" <<'EOF'
 import json, sys
 cfg, u, rep = sys.argv[1:]
-d = json.loads(open(f"gpurun_out/scanu_ab/{cfg}_u{u}_{rep}.json").read().strip().splitlines()[-1])
+d = json.loads(open(f"bench_out/scanu_ab/{cfg}_u{u}_{rep}.json").read().strip().splitlines()[-1])
 k = d["pass"]["kernels"]
 print(cfg, "U", u, "rep", rep, "ms/step", d["ms_per_step"], "one_stream", d.get("one_stream_ms_per_step"),
       "prep_scan", round(k.get("prep_scan", {}).get("avg_ms", 0), 4),

@@ -45,7 +45,7 @@ def main():
     # per-dispatch WRITE_SIZE of the memsets (hipMemsetAsync -> fillBufferAligned) and the group
     # kernel's dispatch count: the step's memsets (plan flags, candidates, line map) per step
     fills, n_group = [], 0
-    for d in glob.glob(f"gpurun_out/pmc_{tag}_p*"):
+    for d in glob.glob(f"bench_out/pmc_{tag}_p*"):
         for f in glob.glob(d + "/**/*counter_collection.csv", recursive=True):
             for r in csv.DictReader(open(f)):
                 key = (short(r["Kernel_Name"]), r["Counter_Name"])
@@ -86,7 +86,7 @@ def main():
     res["step_kernels"] = sorted(k for k in res["kernels"]
                                  if (k.startswith("k_fq") if kind == "fastq" else k in STEP_KERNELS))
     res["method"] = ("TCC_EA0_RDREQ_{32B,64B,128B} x size + TCC_EA0_WRREQ{,_64B}; three rocprofv3 --pmc passes "
-                     "(tools/gpu_pmc_step.sh) over bench.py --steps 3, mean over dispatches; step = the kernels of "
+                     "(tools/gpu_pmc_step.sh) over bench.py --full --steps 3, mean over dispatches; step = the kernels of "
                      "one fresh-batch step, replan + run + indel tally (step_kernels), one launch each, plus "
                      "memset_bytes_per_step (WRITE_SIZE of the fills under 64 MB per group-kernel dispatch)")
     json.dump(res, open(out, "w"), indent=1)

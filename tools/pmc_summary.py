@@ -29,7 +29,7 @@ def per_kernel(path):
 def main():
     tag, sub, bench_name, reads, out = sys.argv[1], sys.argv[2], sys.argv[3], int(sys.argv[4]), sys.argv[5]
     vals = {}
-    for d in glob.glob(f"gpurun_out/pmc_{tag}_*"):
+    for d in glob.glob(f"bench_out/pmc_{tag}_*"):
         f = glob.glob(d + "/**/*counter_collection.csv", recursive=True)
         if not f:
             continue
@@ -46,7 +46,7 @@ def main():
            "fetch_size_kb": vals.get("FETCH_SIZE"), "write_size_kb": vals.get("WRITE_SIZE"),
            "counters_per_launch": vals,
            "method": "TCC_EA0_RDREQ_{32B,64B,128B} x size + TCC_EA0_WRREQ{,_64B}; one rocprofv3 --pmc pass "
-                     "per counter over bench.py --steps 3 (tools/gpu_profile.sh), mean over dispatches"}
+                     "per counter over bench.py --full --steps 3 (tools/gpu_profile.sh), mean over dispatches"}
     json.dump(res, open(out, "w"), indent=1)
     print(json.dumps(res))
 

@@ -232,8 +232,10 @@ inline __device__ int64_t tid_order_d(int32_t t) { return t < 0 ? (int64_t)INT32
 // records run from the region's first candidate; the region ends at the first record of another
 // sequence or at pos >= end (info[0] = its index; info[1] = the same when that record's sequence
 // comes before the region's: the index pointed before its sequence); a record before it is kept when
-// bam_endpos > beg (htslib's overlap test). info[2] = 1: a record's CIGAR passes its block (the host
-// decoder reports it).
+// bam_endpos > beg (htslib's overlap test). info[2] = the first record of the region's sequence with
+// pos < end whose fields pass its block (the host walk's predicate, record_fields_fit: name, CIGAR,
+// sequence and qualities; its CIGAR is not read here). The host walk reports it when it comes before
+// the region's end, kept or not; a later one it never meets.
 __global__ void __launch_bounds__(kBamThreads) k_region_keep(const uint8_t *__restrict__ d, int64_t n,
                                                              const int64_t *__restrict__ rec, int64_t nr, int32_t tid,
                                                              int64_t beg, int64_t end, uint8_t *__restrict__ keep,
@@ -252,9 +254,10 @@ __global__ void __launch_bounds__(kBamThreads) k_region_keep(const uint8_t *__re
   const int l_rn = d[o + 12];
   const int nc = (int)(d[o + 16] | (d[o + 17] << 8));
   const int flag = (int)(d[o + 18] | (d[o + 19] << 8));
-  if (36 + (int64_t)l_rn + 4LL * nc > 4 + (int64_t)bs) {
+  const int32_t lseq = (int32_t)rd32(d, o + 20);
+  if (lseq < 0 || 32 + (int64_t)l_rn + 4LL * nc + ((int64_t)lseq + 1) / 2 + lseq > (int64_t)bs) {
     keep[i] = 1;
-    info[2] = 1;   // (plain store of a constant: any writer's value is the same)
+    __hip_atomic_fetch_min(info + 2, (unsigned long long)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return;
   }
   int64_t rl = 0;
@@ -443,8 +446,8 @@ T *carve(uint8_t *&at, int64_t count) {
 
 // A region read's request (ganon_region_decode): the records of sequence tid overlapping [beg, end)
 // from the window's first record on. status out: 1 the region ends inside the window (the columns
-// are its records'), 0 it goes on past the window, 2 declined — the window holds a malformed record
-// or the index pointed before the sequence: the host's walk reports those.
+// are its records'), 0 it goes on past the window, 2 declined — a malformed record before the region's
+// end or the index pointed before the sequence: the host's walk reports those.
 struct RegionReq {
   int32_t tid;
   int64_t beg, end;
@@ -551,8 +554,8 @@ int columns(ganon_ctx *ctx, const uint8_t *d, int64_t p, int64_t n, ganon_bam_dc
     sel = static_cast<int64_t *>(dalloc((size_t)(nr + 1) * 8));
     int64_t *cnt = static_cast<int64_t *>(dalloc(8));
     if (!all || !keep || !ri || !sel || !cnt) return fail(ctx, GANON_E_DEVICE, "ganon_region_decode: device allocation failed");
-    const unsigned long long init[3] = {~0ull, ~0ull, 0ull};
-    unsigned long long info[3] = {~0ull, ~0ull, 0ull};
+    const unsigned long long init[3] = {~0ull, ~0ull, ~0ull};
+    unsigned long long info[3] = {~0ull, ~0ull, ~0ull};
     HIP_OR_FAIL(hipMemcpyAsync(ri, init, sizeof init, hipMemcpyHostToDevice, s));
     if (nr) {
       {
@@ -570,7 +573,10 @@ int columns(ganon_ctx *ctx, const uint8_t *d, int64_t p, int64_t n, ganon_bam_dc
       HIP_OR_FAIL(ganon_detail::readback(info, ri, sizeof info, s));
       HIP_OR_FAIL(ganon_detail::sync_stream(s));
     }
-    if (info[2] || (info[1] != ~0ull && info[1] == info[0])) {
+    // declined: a malformed record before the region's end (before nr when the region ends with the
+    // window's records: one after the region's end the host walk never reads), or an index that
+    // pointed before its sequence
+    if ((info[2] != ~0ull && (info[0] == ~0ull || info[2] < info[0])) || (info[1] != ~0ull && info[1] == info[0])) {
       rg->status = 2;
       return GANON_OK;
     }

@@ -794,8 +794,19 @@ int scan_tid(ganon_bam_reader *R, int64_t voff, int32_t tid, int64_t hint, ScanB
   }
 }
 
+// Do the name, CIGAR, sequence and qualities of the record at d (block_size first, >= 32 and inside
+// the stream) lie inside its block? records_to_columns' predicate.
+bool record_fields_fit(const uint8_t *d) {
+  int32_t bs, lseq;
+  uint16_t ncig;
+  std::memcpy(&bs, d, 4);
+  std::memcpy(&ncig, d + 16, 2);
+  std::memcpy(&lseq, d + 20, 4);
+  return lseq >= 0 && 32 + (int64_t)d[12] + 4LL * ncig + ((int64_t)lseq + 1) / 2 + lseq <= bs;
+}
+
 // Record end (bam_endpos: pos + reference length, pos + 1 without one or when unmapped) of the
-// record at d (block_size first).
+// record at d (block_size first, its fields inside its block: record_fields_fit).
 int64_t record_end(const uint8_t *d) {
   int32_t pos, l_rn_mq_bin, flag_nc;
   std::memcpy(&pos, d + 8, 4);
@@ -855,6 +866,8 @@ int scan_region(ganon_bam_reader *R, int64_t voff, int32_t tid, int64_t beg, int
         lap(kPhWalk, tw);
         return 0;
       }
+      // (any walked record, kept or not, as bam_read1: record_end reads the CIGAR)
+      if (!record_fields_fit(&data[(size_t)dpos])) return set_err("record fields exceed block size");
       if (record_end(&data[(size_t)dpos]) > beg) recs.push_back(dpos);
       dpos += 4 + bs;
     }

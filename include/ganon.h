@@ -425,8 +425,8 @@ GANON_API int ganon_bam_dcols_free(ganon_ctx *ctx, ganon_bam_dcols *c);
  * region ends inside the window: *cols = the kept records' columns (ganon_bam_view's record fields
  * and blobs, same values and layout as the host decoder's) in one page-locked block *block, freed
  * with ganon_pinned_free. Returns 0 when the region goes on past the window, or the window holds
- * what the host decoder must report (a malformed record, an index that points before the
- * sequence): out[0, out_total) then holds the inflated window for the host's walk. -1: the inflate
+ * what the host decoder must report (a malformed record before the region's end, an index that
+ * points before the sequence): out[0, out_total) then holds the inflated window for the host's walk. -1: the inflate
  * failed. Since ABI 5 (round 6). */
 struct ganon_bam_view;
 GANON_API int ganon_region_decode(void *user, const uint8_t *comp, int64_t comp_len, const int64_t *in_off,

@@ -5,6 +5,7 @@
 // (tests/test_sanitizers.py). Any sanitizer report aborts with a non-zero status.
 //
 //   sanitize_driver bam FILE...                 decode each file (malformed ones must fail cleanly)
+//   sanitize_driver region SPEC FILE...        region reads (SPEC: "tid beg end" lines) through a reader of each file
 //   sanitize_driver plan T.bam N.bam SPEC       plan a pair, replay its I/O log, format every record
 //   sanitize_driver oracle SEED                 mask a random batch (single- and multi-threaded)
 //   sanitize_driver edit SEED                   indel left-overs on random (and malformed) records, range gathers
@@ -53,6 +54,49 @@ static int run_bam(int argc, char **argv) {
     ++ok;
   }
   std::printf("decoded %d rejected %d\n", ok, bad);
+  return 0;
+}
+
+// Every region of SPEC ("tid beg end" per line) through a ganon_bam_reader of each file: a region
+// whose walk meets a malformed record must fail with an error code.
+static int run_region(const char *spec, int argc, char **argv) {
+  std::vector<long long> rg;
+  FILE *fh = std::fopen(spec, "r");
+  if (!fh) return 2;
+  long long t, b, e;
+  while (std::fscanf(fh, "%lld %lld %lld", &t, &b, &e) == 3) {
+    rg.push_back(t);
+    rg.push_back(b);
+    rg.push_back(e);
+  }
+  std::fclose(fh);
+  int ok = 0, bad = 0;
+  for (int a = 0; a < argc; ++a) {
+    ganon_bam_reader *R = nullptr;
+    if (ganon_bam_reader_open(argv[a], 4, &R) != 0) {
+      std::printf("%s not opened\n", argv[a]);
+      ++bad;
+      continue;
+    }
+    int fok = 0, fbad = 0;
+    uint64_t h = 0;
+    for (size_t k = 0; k + 2 < rg.size(); k += 3) {
+      ganon_bam *bam = nullptr;
+      if (ganon_bam_reader_region(R, (int32_t)rg[k], rg[k + 1], rg[k + 2], &bam) != 0) {
+        ++fbad;
+        continue;
+      }
+      ganon_bam_view v;
+      if (ganon_bam_view_get(bam, &v) == 0) h += touch(v);
+      ganon_bam_close(bam);
+      ++fok;
+    }
+    ganon_bam_reader_close(R);
+    std::printf("%s accepted %d rejected %d %llu\n", argv[a], fok, fbad, (unsigned long long)h);
+    ok += fok;
+    bad += fbad;
+  }
+  std::printf("regions accepted %d rejected %d\n", ok, bad);
   return 0;
 }
 
@@ -296,9 +340,10 @@ static int run_edit(int seed) {
 
 int main(int argc, char **argv) {
   if (argc >= 2 && !std::strcmp(argv[1], "bam")) return run_bam(argc - 2, argv + 2);
+  if (argc >= 4 && !std::strcmp(argv[1], "region")) return run_region(argv[2], argc - 3, argv + 3);
   if (argc >= 5 && !std::strcmp(argv[1], "plan")) return run_plan(argv + 2);
   if (argc >= 3 && !std::strcmp(argv[1], "oracle")) return run_oracle(std::atoi(argv[2]));
   if (argc >= 3 && !std::strcmp(argv[1], "edit")) return run_edit(std::atoi(argv[2]));
-  std::fprintf(stderr, "usage: sanitize_driver bam FILE... | plan T.bam N.bam SPEC | oracle SEED\n");
+  std::fprintf(stderr, "usage: sanitize_driver bam FILE... | region SPEC FILE... | plan T.bam N.bam SPEC | oracle SEED | edit SEED\n");
   return 2;
 }

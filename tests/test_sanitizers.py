@@ -2,8 +2,8 @@
 (ADVICE r1): the BGZF/BAM decoder and FASTQ formatter (csrc/ganon_host.cpp), the scope
 planner (csrc/ganon_plan.cpp) and the C oracle (oracle/ganon_oracle.c), linked into one driver
 executable (tests/sanitize/sanitize_driver.cpp) — no preloading, the sanitizer runtime is linked
-in. Valid pairs are planned and formatted; malformed BGZF/BAM files must be rejected with an error
-code, never read out of bounds. CPU only."""
+in. Valid pairs are planned and formatted; malformed BGZF/BAM files, and region reads whose walk
+meets a malformed record, must be rejected with an error code, never read out of bounds. CPU only."""
 import os
 import shutil
 import struct
@@ -118,6 +118,33 @@ def test_malformed_bam_files_are_rejected_cleanly(driver, tmp_path):
     assert f"decoded " in out
     dec, rej = out.strip().split("\n")[-1].split()[1::2]
     assert int(rej) >= 14
+
+
+def test_region_reads_under_sanitizers(driver, tmp_path):
+    """Region reads through the streamed reader (ganon_bam_reader_region's scan_region): the mixed
+    hand-built file of test_region_reference.py, a copy whose index points contig 1 before its
+    sequence, and the files with one record whose fields pass its block — those regions whose walk
+    meets the record are rejected by error code, the others decoded, no sanitizer report."""
+    import test_region_reference as T
+    small = T.build_mixed(str(tmp_path / "small.bam"), 400, 2_100, 9_000, 5_000, seed=45)
+    stale = T.make_stale(small, str(tmp_path / "stale.bam"))
+    regions = T.mixed_regions(T.ref.parse(small), seed=145)
+    spec = tmp_path / "mixed.txt"
+    spec.write_text("".join(f"{t} {a} {b}\n" for t, a, b in regions))
+    out = _run(driver, "region", str(spec), small, stale).strip().split("\n")
+    n_stale = sum(1 for t, a, b in regions if t == 1 and a < b)
+    assert n_stale > 60
+    assert out[0].split()[1:5] == ["accepted", str(len(regions)), "rejected", "0"], out
+    assert out[1].split()[1:5] == ["accepted", str(len(regions) - n_stale), "rejected", str(n_stale)], out
+    for k, regs in T.MALFORMED.items():
+        files = [T.build_plain(str(tmp_path / f"bad_{patch}_{k}.bam"), k, patch) for patch in T.PATCHES]
+        spec = tmp_path / f"plain{k}.txt"
+        spec.write_text("".join(f"0 {a} {b}\n" for a, b in regs))
+        n_bad = sum(T.walk_passes(k, a, b) for a, b in regs)
+        assert 2 <= n_bad < len(regs)
+        out = _run(driver, "region", str(spec), *files).strip().split("\n")
+        for line in out[:len(files)]:
+            assert line.split()[1:5] == ["accepted", str(len(regs) - n_bad), "rejected", str(n_bad)], out
 
 
 def test_fastq_edit_and_gather_under_sanitizers(driver):

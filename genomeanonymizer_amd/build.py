@@ -44,7 +44,7 @@ def _run(cmd) -> None:
 
 
 HIP_SOURCES = ("ganon_hip.hip", "ganon_prep.hip", "ganon_fastq.hip", "ganon_indel.hip", "ganon_inflate.hip",
-               "ganon_bam.hip")
+               "ganon_bam.hip", "ganon_deflate.hip")
 
 
 def build_hip(force: bool = False) -> str:
@@ -52,7 +52,7 @@ def build_hip(force: bool = False) -> str:
     ganon_indel.hip is the slowest unit)."""
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
     hdrs = [os.path.join(REPO, "include", "ganon.h"), os.path.join(CSRC, "ganon_ctx.h"), os.path.join(CSRC, "ganon_batch.h"),
-            __file__]
+            os.path.join(CSRC, "ganon_deflate_core.h"), __file__]
     if not (force or _stale(HIP_LIB, srcs + hdrs)):
         return HIP_LIB
     objdir = os.path.join(PKG, "build")

@@ -25,6 +25,9 @@ int ganon_inflate_impl(ganon_ctx *ctx, const uint8_t *comp, int64_t comp_len, co
                        const int32_t *in_len, const int64_t *out_off, const int32_t *out_len, int64_t n_blocks,
                        uint8_t *out, int64_t out_total, int64_t *first_bad);
 
+struct ganon_deflate_state;                       // ganon_deflate.hip: grow-only device buffers
+void ganon_deflate_free(ganon_deflate_state *st);
+
 struct ganon_ctx {
   int device = 0;
   hipStream_t own = nullptr;
@@ -63,6 +66,7 @@ struct ganon_ctx {
   std::multimap<size_t, void *> dcache;
   size_t dcache_bytes = 0;
   ganon_inflate_state *inflate = nullptr;   // BGZF inflate buffers (first ganon_inflate)
+  ganon_deflate_state *deflate = nullptr;   // BGZF deflate buffers (first ganon_deflate_bgzf)
   // GANON_INDEL_FORK=1: the indel tally of a batch runs on a side stream forked after the batch's
   // prep (fork_ev, recorded by ganon_batch_run before the group kernel) and joined back (join_ev), so
   // that its latency-bound launches overlap the bandwidth-bound group kernel (they read only the

@@ -2197,6 +2197,7 @@ GANON_API int ganon_ctx_destroy(ganon_ctx *ctx) {
   if (ctx->join_ev) hipEventDestroy(ctx->join_ev);
   for (auto &b : ctx->dcache) hipFree(b.second);
   ganon_inflate_free(ctx->inflate);
+  ganon_deflate_free(ctx->deflate);
   delete ctx;
   return GANON_OK;
 }

@@ -2,10 +2,13 @@
 
   python -m genomeanonymizer_amd.genome_anonymizer -d DIR -s samples.tsv -r ref.fa \\
       [-m complete_germline] [-c CPUS] [--record_statistics] [--enhanced_multiprocessing] [-v N]
+      [--compress_output]
 
 samples.tsv: tumor<TAB>normal<TAB>vcf per line, paths relative to DIR, '#' lines skipped.
 Outputs next to the inputs: re.sub('.bam|.sam|.cram', '.anonymized', path) + .1/.2.fastq
 (+ .single_end.fastq), and {normal_bam}.statistics.txt with --record_statistics.
+--compress_output (an extension: the reference writes plain FASTQ) writes .1/.2/.single_end.fastq.gz
+instead, BGZF members deflated on the GPU; GANON_COMPRESS_OUTPUT=1 is the same default.
 
 Multi-GPU: launch under ``torchrun --nproc-per-node N`` (or set WORLD_SIZE/RANK/LOCAL_RANK):
 contigs are sharded round-robin over the ranks; each rank decodes, masks and writes its own
@@ -47,6 +50,8 @@ def exec_parser(argv=None):
                         help="Record statistics about the number of anonymized variants by region and type")
     parser.add_argument("--enhanced_multiprocessing", action=BooleanOptionalAction,
                         help="Accepted for compatibility; no effect (see SURVEY Q12)")
+    parser.add_argument("--compress_output", action=BooleanOptionalAction,
+                        help="Write BGZF-compressed .fastq.gz files, deflated on the GPU (default: GANON_COMPRESS_OUTPUT)")
     parser.add_argument("-v", "--verbose", type=int, required=False, default=2, help="Verbosity of logging")
     parser.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     return parser.parse_args(argv)
@@ -80,6 +85,8 @@ def run_anonymizer(argv=None) -> None:
     if config.method not in ANONYMIZER_ALGORITHMS:
         logging.error("Anonymizer algorithm %s is not a valid option", config.method)
         sys.exit(1)
+    if config.compress_output is not None:   # (the environment reaches spawned pair workers and every rank's paths)
+        os.environ["GANON_COMPRESS_OUTPUT"] = "1" if config.compress_output else "0"
     vcfs, samples, outputs = read_samples(join_dir_file(config.directory, config.samples), config.directory)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))

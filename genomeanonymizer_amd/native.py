@@ -213,6 +213,9 @@ def hip_lib():
     lib.ganon_bam_dcols_get.argtypes = [_p, C.POINTER(BamCols), _i64p]
     lib.ganon_bam_dcols_download.argtypes = [_p, _p, C.POINTER(BamCols)]
     lib.ganon_bam_dcols_free.argtypes = [_p, _p]
+    lib.ganon_deflate_bound.argtypes = [C.c_int64, C.c_int32]
+    lib.ganon_deflate_bound.restype = C.c_int64
+    lib.ganon_deflate_bgzf.argtypes = [_p, _u8p, C.c_int64, C.c_int32, _u8p, C.c_int64, _i64p, _i32p]
     if lib.ganon_abi_version() != 5:
         raise GanonError("libganon_hip.so ABI version mismatch")
     _hip = lib
@@ -249,6 +252,7 @@ EXPORTED_HIP_SYMBOLS = (
     "ganon_inflate", "ganon_inflate_hostcb", "ganon_inflate_device_output",
     "ganon_bam_columns", "ganon_bam_dcols_get", "ganon_bam_dcols_download", "ganon_bam_dcols_free",
     "ganon_pinned_alloc", "ganon_pinned_free", "ganon_pinned_stats", "ganon_region_decode",
+    "ganon_deflate_bound", "ganon_deflate_bgzf",
 )
 EXPORTED_HOST_SYMBOLS = (
     "ganon_bam_open", "ganon_bam_view_get", "ganon_bam_error", "ganon_bam_close",
@@ -423,6 +427,151 @@ class PinnedPool:
 
 
 PINNED = PinnedPool()
+
+BGZF_BLOCK_IN = 0xFF00   # input bytes per BGZF member (bgzip's block size)
+# the 28-byte empty member that ends a BGZF file (SAM specification §4.1.2)
+from .synth.bamwriter import _BGZF_EOF as BGZF_EOF  # noqa: E402
+
+
+def compress_output_default() -> bool:
+    """``GANON_COMPRESS_OUTPUT=1``: BGZF-compressed FASTQ output (``--compress_output``) for library
+    callers and for spawned pair workers and ranks."""
+    return os.environ.get("GANON_COMPRESS_OUTPUT", "0") == "1"
+
+
+def _as_stream(buffers) -> np.ndarray:
+    """bytes, a uint8 array, or a list of them taken as one stream -> one contiguous uint8 array."""
+    if isinstance(buffers, (list, tuple)):
+        parts = [np.frombuffer(b, np.uint8) if not isinstance(b, np.ndarray) else np.ascontiguousarray(b, np.uint8).reshape(-1)
+                 for b in buffers if len(b)]
+        if len(parts) == 1:
+            return parts[0]
+        return np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    if isinstance(buffers, np.ndarray):
+        return np.ascontiguousarray(buffers, np.uint8).reshape(-1)
+    return np.frombuffer(buffers, np.uint8)
+
+
+class GpuDeflater:
+    """BGZF deflate on the GPU (``ganon_deflate_bgzf``, include/ganon.h): a device
+    context of its own (own stream, own grow-only buffers), used by one thread at a time — the
+    output writer hands it a job's bytes per file and appends the members it returns."""
+
+    def __init__(self, device: int = 0):
+        lib = hip_lib()
+        self._lib = lib
+        h = _p()
+        if lib.ganon_ctx_create(int(device), C.byref(h)) != 0:
+            raise GanonError(f"ganon_ctx_create(device={device}) failed: no usable gfx950 device")
+        self._h = h
+        self.device = device
+
+    def set_profiling(self, on: bool) -> None:
+        self._lib.ganon_ctx_set_profiling(self._h, 1 if on else 0)
+
+    def kernel_ms(self) -> float:
+        """k_deflate's time in the last profiled call (HIP events on the context's stream)."""
+        arr = (KernelTime * 4)()
+        n = self._lib.ganon_last_kernel_times(self._h, arr, 4)
+        return sum(float(arr[i].ms) for i in range(min(n, 4)) if arr[i].name == b"k_deflate")
+
+    def bgzf(self, buffers, block_in: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """The stream as whole BGZF members, one per ``block_in`` (0: 0xFF00) bytes: (the members back
+        to back as a uint8 array, page-locked where it can be; their sizes). No EOF member."""
+        src = _as_stream(buffers)
+        n = len(src)
+        bi = int(block_in) or BGZF_BLOCK_IN
+        if not 1 <= bi <= BGZF_BLOCK_IN:
+            raise GanonError(f"bgzf: block_in {block_in} outside 1..0xFF00")
+        sizes = np.zeros(-(-n // bi), np.int32)
+        if n == 0:
+            return np.zeros(0, np.uint8), sizes
+        cap = int(self._lib.ganon_deflate_bound(n, bi))
+        out = PINNED.take(cap)
+        out_len = C.c_int64(0)
+        rc = self._lib.ganon_deflate_bgzf(self._h, _ptr(src, _u8p), n, bi, _ptr(out, _u8p), cap, C.byref(out_len),
+                                          _ptr(sizes, _i32p))
+        if rc != 0:
+            msg = self._lib.ganon_last_error(self._h).decode(errors="replace")
+            raise GanonError(f"ganon_deflate_bgzf failed ({rc}): {msg}")
+        return out[:int(out_len.value)], sizes
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.ganon_ctx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_DEFLATERS: Dict[int, "GpuDeflater"] = {}   # device -> this process's deflater (kept for the next run)
+
+
+def deflater_for(engine, device: int):
+    """The deflater of a run whose masking engine is ``engine``: the GPU's when the engine is (None:
+    the default HipMasker, not created yet) — a failure to create it is an error, never a quiet
+    fall-back to zlib — else the zlib one (the CPU oracle engine of the tests)."""
+    if engine is None or isinstance(engine, HipMasker):
+        d = _DEFLATERS.get(device)
+        if d is None or not d._h:
+            d = _DEFLATERS[device] = GpuDeflater(device)
+        return d
+    return ZlibDeflater()
+
+
+class ZlibDeflater:
+    """The GpuDeflater's interface on Python's zlib (a small thread pool; zlib releases the GIL): for
+    runs whose engine is not the GPU's (the CPU oracle engine of the tests, ``E2E_ENGINE=oracle``).
+    A GPU run never uses it."""
+
+    def __init__(self, level: int = 1, threads: int = 4):
+        self.level = int(level)
+        self._threads = max(1, int(threads))
+        self._pool = None
+
+    def _member(self, block) -> bytes:
+        import struct
+        import zlib
+        c = zlib.compressobj(self.level, zlib.DEFLATED, -15)
+        pay = c.compress(block) + c.flush()
+        if len(pay) >= len(block) + 5:       # a stored block: never more than 31 bytes over the input
+            n = len(block)
+            pay = b"\x01" + struct.pack("<HH", n, n ^ 0xFFFF) + bytes(block)
+        size = 18 + len(pay) + 8
+        return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", size - 1) + pay +
+                struct.pack("<II", zlib.crc32(block), len(block)))
+
+    def set_profiling(self, on: bool) -> None:
+        pass
+
+    def kernel_ms(self) -> float:
+        return 0.0
+
+    def bgzf(self, buffers, block_in: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        src = _as_stream(buffers)
+        bi = int(block_in) or BGZF_BLOCK_IN
+        if not 1 <= bi <= BGZF_BLOCK_IN:
+            raise GanonError(f"bgzf: block_in {block_in} outside 1..0xFF00")
+        mv = memoryview(src)
+        blocks = [mv[i:i + bi] for i in range(0, len(src), bi)]
+        if len(blocks) > 1 and self._threads > 1:
+            if self._pool is None:
+                from concurrent.futures import ThreadPoolExecutor
+                self._pool = ThreadPoolExecutor(self._threads, thread_name_prefix="ganon-zlib")
+            members = list(self._pool.map(self._member, blocks))
+        else:
+            members = [self._member(b) for b in blocks]
+        sizes = np.array([len(m) for m in members], np.int32)
+        return np.frombuffer(b"".join(members), np.uint8), sizes
+
+    def close(self) -> None:
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
 
 
 class HipMasker:

@@ -6,6 +6,8 @@ Mirrors the reference module of the same name (short_read_tumor_normal_anonymize
 arguments and output files:
   {tumor/normal prefix}.1.fastq / .2.fastq, .single_end.fastq when mates stay unpaired,
   {normal_bam}.statistics.txt with --record_statistics.
+With --compress_output (GANON_COMPRESS_OUTPUT=1) the FASTQ files are BGZF-compressed on the device:
+  {prefix}.1.fastq.gz / .2.fastq.gz / .single_end.fastq.gz, and no plain .fastq is created.
 By default a sample streams contig by contig with bounded memory (stream.py: per-contig decode,
 plan, one device batch, cross-contig pairing resolution, output at the contig's file offsets);
 GANON_WHOLE_SAMPLE=1 selects the whole-sample path below (one plan and one device batch for the
@@ -49,15 +51,18 @@ def get_ref_idxs(fasta: FastaRef) -> Dict[str, int]:
 def anonymize_genome(windows_in_sample: List[Window], tumor_bam_file: str, normal_bam_file: str,
                      ref_genome_file: str, anonymizer: CompleteGermlineAnonymizer, tumor_output_fastq: str,
                      normal_output_fastq: str, record_statistics: bool, available_threads: int = 8,
-                     fasta: FastaRef = None, streaming: bool = None, dist=None) -> dict:
+                     fasta: FastaRef = None, streaming: bool = None, dist=None, compress_output: bool = None) -> dict:
+    from . import native
     fasta = fasta or FastaRef(ref_genome_file)
+    if compress_output is None:
+        compress_output = native.compress_output_default()
     if streaming is None:
         streaming = os.environ.get("GANON_WHOLE_SAMPLE", "0") != "1"
     if streaming or dist is not None:
         from .stream import anonymize_genome_streaming
         timing = anonymize_genome_streaming(windows_in_sample, tumor_bam_file, normal_bam_file, fasta, anonymizer,
                                             tumor_output_fastq, normal_output_fastq, record_statistics,
-                                            available_threads, dist=dist)
+                                            available_threads, dist=dist, compress_output=compress_output)
         log.info("Anonymization complete for samples %s and %s: %s", tumor_output_fastq, normal_output_fastq,
                  timing)
         return timing
@@ -70,7 +75,7 @@ def anonymize_genome(windows_in_sample: List[Window], tumor_bam_file: str, norma
         from .stream import anonymize_genome_streaming
         return anonymize_genome_streaming(windows_in_sample, tumor_bam_file, normal_bam_file, fasta, anonymizer,
                                           tumor_output_fastq, normal_output_fastq, record_statistics,
-                                          available_threads)
+                                          available_threads, compress_output=compress_output)
     t1 = time.time()
     planner = make_planner(tumor, normal, fasta, windows_in_sample)
     try:
@@ -81,12 +86,13 @@ def anonymize_genome(windows_in_sample: List[Window], tumor_bam_file: str, norma
         from .stream import anonymize_genome_streaming
         return anonymize_genome_streaming(windows_in_sample, tumor_bam_file, normal_bam_file, fasta, anonymizer,
                                           tumor_output_fastq, normal_output_fastq, record_statistics,
-                                          available_threads)
+                                          available_threads, compress_output=compress_output)
     t2 = time.time()
     res = anonymizer.anonymize(planner, plan)
     t3 = time.time()
     write_fastqs(plan, res, (tumor, normal), (tumor_output_fastq, normal_output_fastq),
-                 backend=anonymizer.format_fastq)
+                 backend=anonymizer.format_fastq,
+                 deflater=native.deflater_for(anonymizer._engine, anonymizer.device) if compress_output else None)
     if record_statistics:
         write_statistics(f"{normal_bam_file}.statistics.txt", statistics_rows(plan, res))
     t4 = time.time()
@@ -102,7 +108,7 @@ def run_short_read_tumor_normal_anonymizer(vcf_variants_per_sample: Sequence[str
                                            ref_genome_file: str, anonymizer: CompleteGermlineAnonymizer,
                                            output_filenames: Sequence[Tuple[str, str]], record_statistics: bool,
                                            cpus: int = 1, enhance_parallelization: bool = False,
-                                           dist=None) -> List[dict]:
+                                           dist=None, compress_output: bool = None) -> List[dict]:
     """SR:889-967. Several pairs run concurrently like the reference's process pool (SR:944-961):
     min(cpus, pairs) processes (GANON_PAIR_WORKERS overrides; 1 = in turn), each with its own HIP
     context on the anonymizer's device, the host threads split as the reference splits
@@ -127,21 +133,24 @@ def run_short_read_tumor_normal_anonymizer(vcf_variants_per_sample: Sequence[str
         # spawned: a forked child of a process that touched the GPU cannot use it
         with ProcessPoolExecutor(max_workers=min(workers, len(inputs)), mp_context=mp.get_context("spawn")) as ex:
             futs = [ex.submit(_anonymize_pair, windows, t_bam, n_bam, ref_genome_file, anonymizer.device, t_out, n_out,
-                              record_statistics, threads)
+                              record_statistics, threads, compress_output)
                     for windows, (t_bam, n_bam), (t_out, n_out) in inputs]
             return [f.result() for f in futs]
     timings = []
     for windows, (t_bam, n_bam), (t_out, n_out) in inputs:
         timings.append(anonymize_genome(windows, t_bam, n_bam, ref_genome_file, anonymizer, t_out, n_out,
-                                        record_statistics, max(1, int(cpus)), fasta=fasta, dist=dist))
+                                        record_statistics, max(1, int(cpus)), fasta=fasta, dist=dist,
+                                        compress_output=compress_output))
     return timings
 
 
-def _anonymize_pair(windows, t_bam, n_bam, ref_genome_file, device, t_out, n_out, record_statistics, threads) -> dict:
+def _anonymize_pair(windows, t_bam, n_bam, ref_genome_file, device, t_out, n_out, record_statistics, threads,
+                    compress_output=None) -> dict:
     """One pair in a pool process (its own HIP context on ``device``)."""
     anon = CompleteGermlineAnonymizer(device=device)
     try:
-        return anonymize_genome(windows, t_bam, n_bam, ref_genome_file, anon, t_out, n_out, record_statistics, threads)
+        return anonymize_genome(windows, t_bam, n_bam, ref_genome_file, anon, t_out, n_out, record_statistics, threads,
+                                compress_output=compress_output)
     finally:
         eng = getattr(anon, "_engine", None)
         if eng is not None and hasattr(eng, "close"):

@@ -133,6 +133,96 @@ def _pwrite_all(fd: int, data, offset: int) -> None:
         parts = ([batch[k][n:]] if k < len(batch) else []) + batch[k + 1:] + parts[len(batch):]
 
 
+def _write_all(fd: int, data) -> None:
+    """Append ``data`` (bytes-like) to ``fd``."""
+    mv = memoryview(data).cast("B")
+    while len(mv):
+        mv = mv[os.write(fd, mv):]
+
+
+def _copy_range(src_fd: int, src_off: int, dst_fd: int, dst_off: int, n: int) -> None:
+    while n > 0:
+        b = os.pread(src_fd, min(n, 8 << 20), src_off)
+        if not b:
+            raise OSError(f"spool ends at offset {src_off}, {n} bytes short")
+        _pwrite_all(dst_fd, b, dst_off)
+        src_off += len(b)
+        dst_off += len(b)
+        n -= len(b)
+
+
+def _agree(comm: "_Comm", err: Optional[BaseException]) -> None:
+    """Every rank learns whether any failed in the last step (one small gather) and raises then."""
+    flags = comm.allgather(repr(err) if err is not None else None)
+    if err is not None:
+        raise err
+    bad = [f for f in flags if f is not None]
+    if bad:
+        raise RuntimeError(f"another rank failed: {bad[0]}")
+
+
+def _assemble_compressed(comm: "_Comm", paths, spools, spool_fds, segs, coord, deflater, single_paths) -> None:
+    """End of a compressed sample. Every rank's spools hold, per file, the BGZF members
+    of its jobs in job order (``segs``: job, file, spool offset, length). The ranks gather the
+    per-job compressed lengths; a job's final offset in a file is the prefix sum in job order. One
+    rank: the spool is the file (tail and EOF member appended, renamed). Several: rank 0 creates the
+    files, every rank copies its segments to their offsets, rank 0 adds the coordinator's tail and
+    the EOF member. Rank 0 writes the single-end files."""
+    rank, world = comm.rank, comm.world
+    lens: Dict[int, List[int]] = {}
+    for job, f, _, n in segs:
+        lens.setdefault(job, [0, 0, 0, 0])[f] = n
+    all_lens: Dict[int, List[int]] = {}
+    for part in comm.allgather(lens):
+        all_lens.update(part)
+    offs: Dict[int, List[int]] = {}
+    total = [0, 0, 0, 0]
+    for job in sorted(all_lens):
+        offs[job] = list(total)
+        for f in range(4):
+            total[f] += all_lens[job][f]
+
+    def members(blob) -> bytes:
+        return (deflater.bgzf(blob)[0].tobytes() if len(blob) else b"") + native.BGZF_EOF
+
+    err = None
+    try:
+        if world == 1:
+            for f in range(4):
+                _write_all(spool_fds[f], members(coord.tail[f]))
+                os.replace(spools[f], paths[f])
+        elif rank == 0:
+            for p in paths:
+                open(p, "wb").close()
+        if rank == 0 and coord.single is not None:
+            for path, blob in zip(single_paths, coord.single):
+                with open(path, "wb") as fh:
+                    fh.write(members(blob))
+    except BaseException as e:   # noqa: BLE001 (agreed on below)
+        err = e
+    if world == 1:
+        if err is not None:
+            raise err
+        return
+    _agree(comm, err)
+    out: List[int] = []
+    src: List[int] = []
+    try:
+        out = [os.open(p, os.O_WRONLY) for p in paths]
+        src = [os.open(p, os.O_RDONLY) for p in spools]
+        for job, f, off, n in segs:
+            _copy_range(src[f], off, out[f], offs[job][f], n)
+        if rank == 0:
+            for f in range(4):
+                _pwrite_all(out[f], members(coord.tail[f]), total[f])
+    except BaseException as e:   # noqa: BLE001
+        err = e
+    finally:
+        for fd in out + src:
+            os.close(fd)
+    _agree(comm, err)
+
+
 @dataclasses.dataclass(frozen=True)
 class JobSpec:
     """One unit of the streamed sample: a FASTA contig, or a run of consecutive sections of it (job
@@ -952,7 +1042,12 @@ class _Coordinator:
     sizes follow from the owner's own write sizes and the resolved writes: no round trip). At the
     end it writes the tail (``pair_unmapped_mates``) and the single ends (SR:561-622)."""
 
-    def __init__(self, fds, paths_single, block_size: int):
+    def __init__(self, fds, paths_single, block_size: int, defer: bool = False):
+        # defer (compressed output): finish() keeps the tail's and the single ends' plain bytes
+        # (``tail``, ``single``) for _assemble_compressed instead of writing them
+        self.defer = defer
+        self.tail: List[bytes] = [b"", b"", b"", b""]
+        self.single: Optional[List[bytes]] = None
         self.fds = fds
         self.paths_single = paths_single
         self.block = block_size
@@ -1066,6 +1161,11 @@ class _Coordinator:
             return b if b is not None else self.carry[k[:4] + (0,)]
         for w in tail.tolist():
             per_file[2 * w[0] + w[1]].append(carried((w[2], w[3], w[4], w[5], w[6])))
+        if self.defer:
+            self.tail = [b"".join(per_file[f]) for f in range(4)]
+            if wse:
+                self.single = [b"".join(carried(tuple(x)) for x in single[d].tolist()) for d in range(2)]
+            return
         for f in range(4):
             blob = b"".join(per_file[f])
             if blob:
@@ -1083,25 +1183,51 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
                                anonymizer: CompleteGermlineAnonymizer, tumor_out: str, normal_out: str,
                                record_statistics: bool, threads: int = 8, dist=None,
                                normal_stats_path: Optional[str] = None, block_size: Optional[int] = None,
-                               window_bytes: int = 0) -> dict:
+                               window_bytes: int = 0, compress_output: Optional[bool] = None) -> dict:
     """One tumor/normal pair, contig by contig (single rank when ``dist`` is None, else the
     ranks of the initialised torch.distributed world, each on its own contigs: distributed.py).
-    Output files, statistics and errors are the reference's (SR:625-760)."""
+    Output files, statistics and errors are the reference's (SR:625-760). ``compress_output``
+    (None: GANON_COMPRESS_OUTPUT): the files are ``.fastq.gz``, BGZF members deflated job by job
+    into per-rank spools and assembled at the end (_assemble_compressed); their decompressed bytes
+    are the plain run's."""
     from .distributed import Link, assign_contigs
     t_start = time.time()
     comm = _Comm(dist)
     rank, world = comm.rank, comm.world
     paths = [f"{tumor_out}.1.fastq", f"{tumor_out}.2.fastq", f"{normal_out}.1.fastq", f"{normal_out}.2.fastq"]
+    single_paths = (f"{tumor_out}.single_end.fastq", f"{normal_out}.single_end.fastq")
+    compress = native.compress_output_default() if compress_output is None else bool(compress_output)
+    deflater = None
+    spools: List[str] = []
+    segs: List[Tuple[int, int, int, int]] = []   # (job, file, spool offset, compressed length) of this rank's jobs
+    spool_len = [0, 0, 0, 0]
+    if compress:
+        # (the engine's deflater: the GPU's for the HIP engine, an error if it cannot be made)
+        deflater = native.deflater_for(anonymizer._engine, anonymizer.device)
+        paths = [p + ".gz" for p in paths]
+        single_paths = tuple(p + ".gz" for p in single_paths)
+        spools = [f"{p}.spool{rank}" for p in paths]
     if block_size is None:
         block_size = _writer.io_block_size(os.path.dirname(os.path.abspath(tumor_out)))
     timing = {"decode_s": 0.0, "plan_s": 0.0, "mask_s": 0.0, "format_s": 0.0, "prefetch_s": 0.0, "resolve_s": 0.0,
               "write_s": 0.0, "wait_s": 0.0, "writer_wait_s": 0.0, "prunes": 0, "jobs": 0, "reads": 0, "bases": 0}
     failure: Optional[BaseException] = None
-    if rank == 0:
+    if rank == 0 and not compress:
         for p in paths:
             open(p, "wb").close()
     comm.barrier()
-    fds = [os.open(p, os.O_WRONLY) for p in paths]
+    fds: List[int] = []
+    try:
+        for p in (spools if compress else paths):
+            fds.append(os.open(p, os.O_WRONLY | os.O_CREAT | os.O_TRUNC | os.O_APPEND, 0o666) if compress
+                       else os.open(p, os.O_WRONLY))
+    except BaseException:
+        for fd in fds:
+            os.close(fd)
+        for p in spools:
+            if os.path.exists(p):
+                os.remove(p)
+        raise
     readers = (BamReader(tumor_bam, threads, window_bytes), BamReader(normal_bam, threads, window_bytes))
     # jobs: contigs, or runs of sections of about GANON_JOB_BP bases (default 4 Mb; 0 = whole
     # contigs) when both BAMs are indexed
@@ -1138,8 +1264,7 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
     t_g = time.time()
     link = Link(dist)
     timing_groups = time.time() - t_g
-    coord = _Coordinator(fds, (f"{tumor_out}.single_end.fastq", f"{normal_out}.single_end.fastq"), block_size) \
-        if rank == 0 else None
+    coord = _Coordinator(fds, single_paths, block_size, defer=compress) if rank == 0 else None
     coord_exc: List[Optional[BaseException]] = [None]
     stats_rows: List[Tuple[int, Dict[str, List[int]]]] = []
     totals = np.zeros(8, np.int64)
@@ -1296,8 +1421,18 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
                     raise RuntimeError(f"job {job.job}: {nb} bytes for file {f}, {res['sizes'][f]} planned")
             # the four files written concurrently (pwrite drops the GIL; a file system serialises
             # buffered writes per file, not across files)
-            futs = [file_pool.submit(_pwrite_all, fds[f], data[f], res["offsets"][f]) for f in range(4)
-                    if any(len(x) for x in data[f])]
+            if deflater is not None:
+                # the job's run of every file as whole members, appended to this rank's spool
+                for f in range(4):
+                    if any(len(x) for x in data[f]):
+                        comp, _ = deflater.bgzf(list(data[f]))
+                        _write_all(fds[f], comp)
+                        segs.append((job.job, f, spool_len[f], len(comp)))
+                        spool_len[f] += len(comp)
+                futs = []
+            else:
+                futs = [file_pool.submit(_pwrite_all, fds[f], data[f], res["offsets"][f]) for f in range(4)
+                        if any(len(x) for x in data[f])]
             for fu in futs:
                 fu.result()
             stats_rows.append((job.job, job.stats()))
@@ -1415,6 +1550,10 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
             if failure is not None:
                 raise failure
             raise RuntimeError(f"another rank failed: {errs[0]}")
+        if compress:
+            t_asm = time.time()
+            _assemble_compressed(comm, paths, spools, fds, segs, coord, deflater, single_paths)
+            timing["assemble_s"] = round(time.time() - t_asm, 3)
         # every rank ended cleanly: its sends all have their receives (a failed run never drains: a
         # failed rank stops receiving). The side groups serve this process's next run only when every
         # rank drained (one more small gather, so that all ranks cache alike and the next
@@ -1456,6 +1595,13 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
             dec_pool.shutdown(wait=True)
         for fd in fds:
             os.close(fd)
+        if isinstance(deflater, native.ZlibDeflater):
+            deflater.close()
+        for p in spools:   # (best effort, on failure too; one rank's were renamed into place)
+            try:
+                os.remove(p)
+            except OSError:
+                pass
         # the readers' file mappings go on a thread of their own (unmapping a chromosome's BAM
         # took part of every rank's tail; nothing waits for it)
         threading.Thread(target=_close_all, args=(list(readers) + list(redo_readers),), daemon=True).start()

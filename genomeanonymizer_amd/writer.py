@@ -477,8 +477,22 @@ def io_block_size(directory: str) -> int:
 
 
 def write_fastqs(plan: Plan, res: MaskResult, tables, prefixes: Tuple[str, str],
-                 block_size: int = None, backend=None) -> Dict[str, int]:
+                 block_size: int = None, backend=None, deflater=None) -> Dict[str, int]:
+    """The sample's FASTQ files; with ``deflater`` (native.GpuDeflater / ZlibDeflater) each file's
+    bytes go through it before the write: ``.fastq.gz``, BGZF members and the EOF member. Returns
+    the plain size of every file written."""
     import os
+
+    def put(path: str, data) -> str:
+        if deflater is not None:
+            path += ".gz"
+            data = [deflater.bgzf(data)[0], native.BGZF_EOF]
+        else:
+            data = [data]
+        with open(path, "wb") as fh:
+            for d in data:
+                fh.write(d)
+        return path
     fmt = FastqFormatter(tables, res, backend)
     if block_size is None:
         block_size = io_block_size(os.path.dirname(os.path.abspath(prefixes[0])))
@@ -497,16 +511,12 @@ def write_fastqs(plan: Plan, res: MaskResult, tables, prefixes: Tuple[str, str],
             path = f"{prefixes[ds]}.{slot + 1}.fastq"
             e = order[2 * ds + slot]
             data = fmt.format_arrays(ids[e], rows[e], isc[e], reapply[e])
-            with open(path, "wb") as fh:
-                fh.write(data)
-            sizes[path] = len(data)
+            sizes[put(path, data)] = len(data)
     if plan.write_single_end:
         for ds in (0, 1):
             path = f"{prefixes[ds]}.single_end.fastq"
             data = fmt.format(plan.single_end[ds], plan.single_reapply[ds])
-            with open(path, "wb") as fh:
-                fh.write(data)
-            sizes[path] = len(data)
+            sizes[put(path, data)] = len(data)
     return sizes
 
 

@@ -434,4 +434,20 @@ GANON_API int ganon_region_decode(void *user, const uint8_t *comp, int64_t comp_
                                   int64_t n_blocks, uint8_t *out, int64_t out_total, int64_t p0, int32_t tid,
                                   int64_t beg, int64_t end, int at_eof, struct ganon_bam_view *cols, void **block);
 
+/* ---- BGZF deflate (compressed FASTQ output; the mirror of ganon_inflate) -----------------------
+ * in[0, in_len) cut into blocks of block_in bytes (0 = 0xFF00; at most 0xFF00), each one complete
+ * BGZF member (18-byte header with the BC subfield, raw DEFLATE payload of RFC 1951, CRC32, ISIZE;
+ * at most 65536 bytes, and at most 31 bytes more than its block: a block that a dynamic-Huffman
+ * block would not shrink is stored). The members lie back to back in out; *out_len = their total;
+ * member_sizes ([ceil(in_len / block_in)], may be NULL) = each member's size. Any concatenation of
+ * whole members is a valid gzip file; the caller appends the 28-byte BGZF EOF member. Host buffers
+ * (page-locked for full rate), synchronous, any in_len (chunked inside; the device buffers are the
+ * context's, grow-only). in_len 0: no member. out_cap must be at least ganon_deflate_bound (in_len
+ * + 31 per block), which returns GANON_E_ARG on a bad argument. The output is a pure function of
+ * the input bytes and block_in. With profiling on, k_deflate (the encoder) and k_deflate_compact
+ * appear in ganon_last_kernel_times. Since ABI 5. */
+GANON_API int64_t ganon_deflate_bound(int64_t in_len, int32_t block_in);
+GANON_API int ganon_deflate_bgzf(ganon_ctx *ctx, const uint8_t *in, int64_t in_len, int32_t block_in,
+                                 uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *member_sizes);
+
 #endif /* GANON_H */

@@ -17,6 +17,8 @@ Prints one JSON line with per-stage seconds, reads/s, bases/s and the process's 
     E2E_WORKERS=P ...        # the streamed path in P processes sharing the GPU (torch.distributed.run,
                              # gloo; the contigs sharded over them as over the ranks of a multi-GPU run,
                              # host decode threads 16 / P each); wall = the slowest rank's
+    GANON_COMPRESS_OUTPUT=1  # BGZF-compressed .fastq.gz output, deflated on the GPU: the same
+                             # line with "compress_output": true, for the price of the flag
     E2E_DISK_PROBE=1 ...     # also time 2 GiB of pwrite into OUTDIR (4 files at once, as the product
                              # writes; page cache, then with fsync): the box's write bandwidth
 """
@@ -118,6 +120,8 @@ def main():
     anon = _engine()
     res = {"windows_s": round(t_win, 3), "engine": os.environ.get("E2E_ENGINE", "hip")}
     modes = sys.argv[3].split(",") if len(sys.argv) > 3 else ["stream", "whole"]
+    from genomeanonymizer_amd import native as _native
+    gz = ".gz" if _native.compress_output_default() else ""
     if dist is not None and modes != ["stream"]:
         sys.exit("E2E_WORKERS > 1 runs the streamed path only")
     threads = int(os.environ.get("E2E_DECODE_THREADS", "0")) or max(1, 16 // workers)
@@ -136,7 +140,7 @@ def main():
                 for x in ("tumor", "normal"):
                     for sfx in (".1.fastq", ".2.fastq", ".single_end.fastq"):
                         try:
-                            os.unlink(os.path.join(out, f"{x}_{mode}{sfx}"))
+                            os.unlink(os.path.join(out, f"{x}_{mode}{sfx}{gz}"))
                         except FileNotFoundError:
                             pass
             if dist is not None:
@@ -205,14 +209,18 @@ def main():
                      "first_run_wall_s": round(runs[0]["wall_s"], 3),
                      # host CPU seconds of all ranks over the run, and the cores that kept busy
                      "cpu_s": round(best["cpu_s"], 2), "cores_busy": round(best["cpu_s"] / best["wall_s"], 2),
+                     "cpu_us_per_read": round(best["cpu_s"] / max(1, best["reads"]) * 1e6, 3),
+                     "compress_output": bool(gz),
                      "cpus_available": len(os.sched_getaffinity(0)),
-                     "output_bytes": sum(os.path.getsize(os.path.join(out, f"{x}_{mode}{s}"))
+                     "output_bytes": sum(os.path.getsize(os.path.join(out, f"{x}_{mode}{s}{gz}"))
                                          for x in ("tumor", "normal") for s in (".1.fastq", ".2.fastq"))}
         if rank == 0:
             print(json.dumps({mode: res[mode]}), file=sys.stderr, flush=True)
     if "stream" in res and "whole" in res:
-        same = all(open(os.path.join(out, f"{x}_stream{s}"), "rb").read() ==
-                   open(os.path.join(out, f"{x}_whole{s}"), "rb").read()
+        import gzip
+        opn = gzip.open if gz else open   # (the plain bytes: the two paths cut their members differently)
+        same = all(opn(os.path.join(out, f"{x}_stream{s}{gz}"), "rb").read() ==
+                   opn(os.path.join(out, f"{x}_whole{s}{gz}"), "rb").read()
                    for x in ("tumor", "normal") for s in (".1.fastq", ".2.fastq"))
         res["stream_equals_whole"] = same
     if rank == 0 and os.environ.get("E2E_DIGEST") == "1":   # (outside the timed runs: A/B parity of settings)
@@ -223,9 +231,11 @@ def main():
                 continue
             for x in ("tumor", "normal"):
                 for sfx in (".1.fastq", ".2.fastq", ".single_end.fastq"):
-                    p = os.path.join(out, f"{x}_{mode}{sfx}")
+                    p = os.path.join(out, f"{x}_{mode}{sfx}{gz}")
                     if os.path.exists(p):
-                        with open(p, "rb") as f:
+                        # (the plain bytes: a compressed run's digest equals the plain run's)
+                        import gzip
+                        with (gzip.open(p, "rb") if gz else open(p, "rb")) as f:
                             for blk in iter(lambda: f.read(1 << 24), b""):
                                 dig.update(blk)
         res["output_sha1"] = dig.hexdigest()

@@ -278,7 +278,9 @@ class CompleteGermlineAnonymizer:
         """FASTQ records on the masking engine's device (``ganon_fastq_format_hip``); an engine
         without a formatter (none in the product) leaves them to libganon_host.so."""
         fmt = getattr(self.engine, "format_fastq", None)
-        if fmt is None:
+        # (--masked_base_quality: a test engine whose formatter predates the option gets the host
+        # library's ganon_fastq_format_mq; HipMasker patches the qualities on the device)
+        if fmt is None or ("maskq" in recs and not getattr(self.engine, "formats_maskq", False)):
             return native.host_format_fastq(recs)
         with self.lock:
             return fmt(recs)

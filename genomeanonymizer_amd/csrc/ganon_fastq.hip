@@ -21,6 +21,8 @@
 //               lookups, reverse complement with a zero-byte test for the Q7 error) and written.
 //   k_fq_quad / k_fq_rows / k_fq_format: earlier designs kept as A/B instances
 //               (GANON_PARAM_FASTQ_KD); k_fq_dense takes tiles with more than 64 records.
+//   k_fq_maskq  (--masked_base_quality only, after ganon_fastq_set_maskq) a post-pass over the
+//               formatted text: the quality under every base an SNV mask wrote becomes '!' + Q.
 #include "ganon_ctx.h"
 
 #include <algorithm>
@@ -1496,6 +1498,159 @@ __global__ void __launch_bounds__(kFqThreads) k_fq_dense(const FqBufs bufs, cons
   if (bad != ~0ull) atomicMin(err, bad);
 }
 
+// ---- masked-base quality post-pass (--masked_base_quality) ---------------------------
+// Runs after the formatter, over its OUTPUT: for every record that has an original (orig[r] != ~0:
+// nibble offset | buffer << 56) and as many qualities as bases, the nibbles of the masked copy are
+// compared with the read's original nibbles, and for every one that differs (an SNV mask wrote the
+// reference base there) the quality character printed under that base — text index p, or L-1-p on a
+// reverse read — becomes qc. The text is patched, not the quality source: two records of one job can
+// share a read's quality bytes and be masked at different positions.
+//
+// A chunk is 16 nibbles of a read in both buffers: the three aligned dwords under it, each clamped
+// into the read's own aligned extent of that buffer (nibbles outside the read are masked off, so a
+// clamped dword never matters and no load leaves the read's bytes rounded out to dwords), nibbles
+// swapped into ascending order and funnel-shifted to the chunk's first nibble; reads start anywhere
+// in either buffer. A workgroup takes kMqGroups consecutive records, one per group of kMqLanes lanes:
+// the group strides over the chunks of a record of up to kMqShort bases (a 150-base read keeps 10 of
+// its 16 lanes busy once, where a wave per read would idle 54 of 64). A longer record is left to its
+// whole wave, which takes its groups' long records in turn with 64 lanes striding (a 100 kb read: 98
+// rounds instead of 391); long-read batches have as many waves as a quarter of their records. No
+// LDS, no barrier; differences are rare, so the byte stores are too. (A first version scanned the
+// workgroup's records for long ones with uniform loads in a loop: 16 dependent scalar loads per
+// workgroup made the kernel 1.7x slower on short reads. Two or four records per lane group with all
+// their loads in flight together gave nothing, 1.05 and 1.43 ms against 1.05: DESIGN §4c.)
+constexpr int kMqLanes = 16;
+constexpr int kMqGroups = kFqThreads / kMqLanes;               // lane groups per workgroup
+constexpr uint32_t kMqShort = 16 * kMqLanes * 4;               // bases: at most 4 rounds of the record's lane group
+
+struct MqBufs {
+  const uint8_t *p[kFqMaxBufs];
+};
+
+// 16 nibbles of a read from nibble `first` on: the addresses of the three aligned dwords under them,
+// each clamped into the read's own aligned extent (!ok: nothing is wanted and they point at `safe`, so
+// that the loads need no branch), and the shift to the first nibble once the dwords are combined.
+struct MqAddr {
+  GU32 *p[3];
+  uint32_t sh;
+};
+
+__device__ __forceinline__ MqAddr mq_addr(const uint8_t *base, uint64_t nib0, uint32_t L, uint32_t first, bool ok,
+                                          uintptr_t safe) {
+  const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+  const uintptr_t lo = (b + (nib0 >> 1)) & ~(uintptr_t)3, hi = (b + ((nib0 + L - 1) >> 1)) & ~(uintptr_t)3;
+  const uint64_t nb = nib0 + first;
+  const uintptr_t a = b + (nb >> 1), aa = a & ~(uintptr_t)3;
+  MqAddr m;
+  m.sh = 4 * (2 * (uint32_t)(a - aa) + (uint32_t)(nb & 1));   // 0..28
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const uintptr_t x = aa + 4 * k;
+    m.p[k] = reinterpret_cast<GU32 *>(ok ? (x < lo ? lo : x > hi ? hi : x) : safe);
+  }
+  return m;
+}
+
+// The loaded dwords as 16 nibbles, nibble j at bits 4j (garbage past the read's end: the caller masks).
+__device__ __forceinline__ uint64_t mq_nibbles(const uint32_t (&x)[3], uint32_t sh) {
+  uint32_t d[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d[k] = ((x[k] & 0x0F0F0F0Fu) << 4) | ((x[k] >> 4) & 0x0F0F0F0Fu);
+  const uint64_t w = (uint64_t)d[0] | ((uint64_t)d[1] << 32);
+  return sh ? (w >> sh) | ((uint64_t)d[2] << (64 - sh)) : w;
+}
+
+// One chunk of one record in flight: addresses, then loads (issue), then the differing nibbles (finish).
+struct MqChunk {
+  MqAddr m, o;
+  uint32_t xm[3], xo[3];
+  bool ok;
+};
+
+__device__ __forceinline__ void mq_issue(MqChunk &c, const FqBufs &bufs, const MqBufs &ob, const FqRec &R, uint64_t o,
+                                         uint32_t first, bool ok, uintptr_t safe) {
+  c.ok = ok & (first < R.len);
+  c.m = mq_addr(pick4(bufs.seq, (uint32_t)(R.seq >> 56) & 3), R.seq & kOff56, R.len, first, c.ok, safe);
+  c.o = mq_addr(pick4(ob.p, (uint32_t)(o >> 56) & 3), o & kOff56, R.len, first, c.ok, safe);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    c.xm[k] = *c.m.p[k];
+    c.xo[k] = *c.o.p[k];
+  }
+}
+
+// One bit per differing nibble, at bits 4j.
+__device__ __forceinline__ uint64_t mq_finish(const MqChunk &c, const FqRec &R, uint32_t first) {
+  if (!c.ok) return 0;
+  uint64_t d = mq_nibbles(c.xm, c.m.sh) ^ mq_nibbles(c.xo, c.o.sh);
+  const uint32_t cnt = min(16u, R.len - first);
+  if (cnt < 16) d &= (1ull << (4 * cnt)) - 1;
+  d |= d >> 1;
+  d |= d >> 2;
+  return d & 0x1111111111111111ull;
+}
+
+__device__ __forceinline__ void mq_store(uint64_t d, const FqRec &R, uint32_t first, uint8_t *__restrict__ q,
+                                         uint32_t qc) {
+  const bool rev = (R.seq >> 58) & 1;
+  while (d) {
+    const uint32_t p = first + ((uint32_t)__builtin_ctzll(d) >> 2);
+    d &= d - 1;
+    q[rev ? R.len - 1 - p : p] = (uint8_t)qc;
+  }
+}
+
+__device__ __forceinline__ void mq_record(const FqBufs &bufs, const MqBufs &ob, const FqRec &R, uint64_t o,
+                                          uint8_t *__restrict__ q, uint32_t qc, uint32_t lane, uint32_t stride,
+                                          uintptr_t safe) {
+  for (uint32_t first = 16 * lane; first < R.len; first += 16 * stride) {
+    MqChunk c;
+    mq_issue(c, bufs, ob, R, o, first, true, safe);
+    mq_store(mq_finish(c, R, first), R, first, q, qc);
+  }
+}
+
+__device__ __forceinline__ bool mq_wanted(const FqRec &R, uint64_t o) {
+  return o != ~0ull && R.len != 0 && R.qlen == R.len;
+}
+
+__device__ __forceinline__ uint8_t *mq_qual(uint8_t *out, uint64_t off, const FqRec &R) {
+  return out + off + (uint32_t)(R.name >> 48) + R.len + 7;
+}
+
+__global__ void __launch_bounds__(kFqThreads) k_fq_maskq(const FqBufs bufs, const MqBufs ob,
+                                                         const FqRec *__restrict__ recs,
+                                                         const uint64_t *__restrict__ orig,
+                                                         const uint64_t *__restrict__ off, int64_t n,
+                                                         uint8_t *__restrict__ out, uint32_t qc) {
+  const uint32_t t = threadIdx.x, gl = t % kMqLanes;
+  const int64_t r = (int64_t)blockIdx.x * kMqGroups + t / kMqLanes;
+  const uintptr_t safe = reinterpret_cast<uintptr_t>(recs);
+  const int64_t rr = r < n ? r : n - 1;
+  const FqRec R = recs[rr];
+  const uint64_t o = orig[rr], of = off[rr];
+  const bool want = (r < n) & (o != ~0ull) & (R.len != 0) & (R.qlen == R.len);
+  const bool shrt = want & (R.len <= kMqShort);
+  // short record: its lane group, the first round's six loads without a branch in front of them
+  MqChunk c;
+  mq_issue(c, bufs, ob, R, o, 16 * gl, shrt, safe);
+  if (shrt) {
+    uint8_t *q = mq_qual(out, of, R);
+    mq_store(mq_finish(c, R, 16 * gl), R, 16 * gl, q, qc);
+    if (R.len > 16 * kMqLanes) mq_record(bufs, ob, R, o, q, qc, gl + kMqLanes, kMqLanes, safe);
+  }
+  // long records: the whole wave over each of its groups' in turn (found by a ballot of the groups'
+  // first lanes; the record is read again, uniformly)
+  unsigned long long m = __ballot(want && !shrt && gl == 0);
+  while (m) {
+    const uint32_t src = (uint32_t)__builtin_ctzll(m);
+    m &= m - 1;
+    const int64_t rl = (int64_t)blockIdx.x * kMqGroups + ((t & ~63u) + src) / kMqLanes;
+    const FqRec L = recs[rl];
+    mq_record(bufs, ob, L, orig[rl], mq_qual(out, off[rl], L), qc, t & 63, 64, safe);
+  }
+}
+
 }  // namespace
 
 // ---- host side ---------------------------------------------------------------------------
@@ -1513,6 +1668,13 @@ struct ganon_fastq {
   int *dense_list = nullptr;          // tiles left to k_fq_dense
   unsigned int *dense_count = nullptr;
   uint8_t *out = nullptr;
+  // --masked_base_quality (ganon_fastq_set_maskq): off unless mq_on
+  int64_t len_sum = 0;                // sum of the records' sequence lengths (set_maskq checks its caller's)
+  int64_t batch_bytes = -1;           // size of a device batch's sequence buffers (-1: host buffers)
+  bool mq_on = false;
+  uint32_t mq_qc = 0;
+  MqBufs mq_bufs{};
+  uint64_t *mq_orig = nullptr;
 };
 
 namespace {
@@ -1591,6 +1753,7 @@ GANON_API int ganon_fastq_upload(ganon_ctx *ctx, const ganon_fastq_records *in, 
     const uint64_t rl = (uint64_t)(8 + NL + L + Q);
     if (rl > UINT32_MAX) return bail(fail(ctx, GANON_E_ARG, "record %lld longer than 4 GiB", (long long)i));
     total += rl;
+    f->len_sum += L;
   }
   if (ne.lo == INT64_MAX) ne.lo = ne.hi = 0;
   for (auto &e : se) if (e.lo == INT64_MAX) e.lo = e.hi = 0;
@@ -1607,6 +1770,7 @@ GANON_API int ganon_fastq_upload(ganon_ctx *ctx, const ganon_fastq_records *in, 
       if (se[s].hi > bytes) return bail(fail(ctx, GANON_E_ARG, "sequence offset past the batch buffer"));
     f->bufs.seq[0] = dout;
     f->bufs.seq[1] = din;
+    f->batch_bytes = bytes;
   } else {
     if (!in->seq_buf) return bail(fail(ctx, GANON_E_ARG, "no sequence buffers"));
     for (int s = 0; s < nsb; ++s) {
@@ -1722,6 +1886,78 @@ GANON_API int ganon_fastq_run(ganon_ctx *ctx, ganon_fastq *f) {
                        f->tile_first, f->n, f->total, f->out, f->err, f->dense_list, f->dense_count);
     if ((rc = check_launch(ctx, "k_fq_format"))) return rc;
   }
+  if (f->mq_on) {   // the post-pass over the formatted text (every instance above writes the same bytes)
+    KernelScope ks(ctx, "k_fq_maskq");
+    hipLaunchKernelGGL(k_fq_maskq, dim3((unsigned)((f->n + kMqGroups - 1) / kMqGroups)), dim3(kFqThreads), 0,
+                       ctx->stream, f->bufs, f->mq_bufs, f->recs, f->mq_orig, f->off, f->n, f->out, f->mq_qc);
+    if ((rc = check_launch(ctx, "k_fq_maskq"))) return rc;
+  }
+  return GANON_OK;
+}
+
+GANON_API int ganon_fastq_set_maskq(ganon_ctx *ctx, ganon_fastq *f, int64_t n, const int32_t *seq_len,
+                                    const uint8_t *const *orig_buf, int32_t n_orig_bufs, const uint8_t *orig_sel,
+                                    const int64_t *orig_nib_off, int32_t quality) {
+  if (!ctx || !f) return GANON_E_ARG;
+  if (quality < 0 || quality > 93) return fail(ctx, GANON_E_ARG, "masked-base quality %d outside 0..93", quality);
+  if (n != f->n || (n && (!seq_len || !orig_sel || !orig_nib_off)))
+    return fail(ctx, GANON_E_ARG, "masked-base quality: arrays do not match the uploaded records");
+  if (f->mq_on) return fail(ctx, GANON_E_ARG, "masked-base quality already set");
+  if (n > (int64_t)INT32_MAX * kMqGroups) return fail(ctx, GANON_E_ARG, "too many records");
+  const bool batch = f->batch_bytes >= 0;
+  const int nob = batch ? 2 : n_orig_bufs;
+  if (nob < 0 || nob > kFqMaxBufs || (!batch && nob && !orig_buf))
+    return fail(ctx, GANON_E_ARG, "masked-base quality: 0..%d original buffers", kFqMaxBufs);
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
+  struct Ext { int64_t lo = INT64_MAX, hi = 0; };
+  Ext oe[kFqMaxBufs];
+  int64_t sum = 0, with = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t L = seq_len[i];
+    if (L < 0) return fail(ctx, GANON_E_ARG, "record %lld: bad length", (long long)i);
+    sum += L;
+    const int s = orig_sel[i];
+    if (s == 255) continue;
+    if (s >= nob || orig_nib_off[i] < 0)
+      return fail(ctx, GANON_E_ARG, "record %lld: bad original buffer or offset", (long long)i);
+    if (!L) continue;
+    ++with;
+    oe[s].lo = std::min(oe[s].lo, orig_nib_off[i] >> 1);
+    oe[s].hi = std::max(oe[s].hi, (orig_nib_off[i] + L + 1) >> 1);
+  }
+  if (sum != f->len_sum) return fail(ctx, GANON_E_ARG, "masked-base quality: lengths differ from the uploaded records");
+  if (!with) return GANON_OK;   // nothing to compare: no launch
+  int rc;
+  int64_t base[kFqMaxBufs] = {0, 0, 0, 0};
+  for (int s = 0; s < kFqMaxBufs; ++s) {
+    f->mq_bufs.p[s] = f->bufs.seq[0];
+    if (s >= nob || oe[s].lo == INT64_MAX) continue;
+    if (batch) {
+      if (oe[s].hi > f->batch_bytes) return fail(ctx, GANON_E_ARG, "original offset past the batch buffer");
+      f->mq_bufs.p[s] = f->bufs.seq[s];
+    } else {
+      if (!orig_buf[s]) return fail(ctx, GANON_E_ARG, "null original buffer %d", s);
+      uint8_t *d = nullptr;
+      const int64_t sz = oe[s].hi - oe[s].lo;
+      if ((rc = fq_alloc(ctx, f, &d, (size_t)sz))) return rc;
+      HIP_OR_FAIL(hipMemcpyAsync(d, orig_buf[s] + oe[s].lo, sz, hipMemcpyHostToDevice, ctx->stream));
+      f->mq_bufs.p[s] = d;
+      base[s] = oe[s].lo;
+    }
+  }
+  std::vector<uint64_t> packed((size_t)n);
+  host_parallel(n, [&](int64_t a, int64_t b) {
+    for (int64_t i = a; i < b; ++i) {
+      const int s = orig_sel[i];
+      packed[i] = (s == 255 || !seq_len[i]) ? ~0ull : (uint64_t)(orig_nib_off[i] - 2 * base[s]) | ((uint64_t)s << 56);
+    }
+  });
+  if ((rc = fq_alloc(ctx, f, &f->mq_orig, (size_t)n))) return rc;
+  HIP_OR_FAIL(hipMemcpyAsync(f->mq_orig, packed.data(), packed.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
+                             ctx->stream));
+  HIP_OR_FAIL(ganon_detail::sync_stream(ctx->stream));   // the host staging vector dies here
+  f->mq_qc = (uint32_t)(33 + quality);
+  f->mq_on = true;
   return GANON_OK;
 }
 
@@ -1763,19 +1999,22 @@ GANON_API int ganon_fastq_free(ganon_ctx *ctx, ganon_fastq *f) {
   return GANON_OK;
 }
 
-GANON_API int64_t ganon_fastq_format_hip(ganon_ctx *ctx, int64_t n, const uint8_t *const *seq_buf,
-                                         const uint8_t *seq_sel, const int64_t *seq_nib_off, const int32_t *seq_len,
-                                         const uint8_t *reverse, const uint8_t *const *qual_buf,
-                                         const uint8_t *qual_sel, const int64_t *qual_off, const int32_t *qual_len,
-                                         const uint8_t *qual_rev, const char *names, const int64_t *name_off,
-                                         const int32_t *name_len, const uint8_t *mate, char *out, int64_t cap) {
+namespace {
+
+int64_t fq_one_shot(ganon_ctx *ctx, int64_t n, const uint8_t *const *seq_buf, const uint8_t *seq_sel,
+                    const int64_t *seq_nib_off, const int32_t *seq_len, const uint8_t *reverse,
+                    const uint8_t *const *qual_buf, const uint8_t *qual_sel, const int64_t *qual_off,
+                    const int32_t *qual_len, const uint8_t *qual_rev, const char *names, const int64_t *name_off,
+                    const int32_t *name_len, const uint8_t *mate, const uint8_t *orig_sel,
+                    const int64_t *orig_nib_off, int32_t quality, char *out, int64_t cap) {
   if (!ctx || n < 0) return GANON_FASTQ_FAILED;
   ganon_fastq_records r{};
   r.n = n;
-  int ms = 0, mq = 0;
+  int ms = 0, mq = 0, mo = -1;
   for (int64_t i = 0; i < n; ++i) {
     ms = std::max<int>(ms, seq_sel[i]);
     mq = std::max<int>(mq, qual_sel[i]);
+    if (orig_sel && orig_sel[i] != 255) mo = std::max<int>(mo, orig_sel[i]);
   }
   r.n_seq_bufs = ms + 1;
   r.n_qual_bufs = mq + 1;
@@ -1795,7 +2034,34 @@ GANON_API int64_t ganon_fastq_format_hip(ganon_ctx *ctx, int64_t n, const uint8_
   r.mate = mate;
   ganon_fastq *f = nullptr;
   if (ganon_fastq_upload(ctx, &r, &f)) return GANON_FASTQ_FAILED;
-  const int64_t w = ganon_fastq_run(ctx, f) ? GANON_FASTQ_FAILED : ganon_fastq_download(ctx, f, out, cap);
+  int64_t w = GANON_FASTQ_FAILED;
+  if (!orig_sel || !ganon_fastq_set_maskq(ctx, f, n, seq_len, seq_buf, mo + 1, orig_sel, orig_nib_off, quality))
+    w = ganon_fastq_run(ctx, f) ? GANON_FASTQ_FAILED : ganon_fastq_download(ctx, f, out, cap);
   ganon_fastq_free(ctx, f);
   return w;
+}
+
+}  // namespace
+
+GANON_API int64_t ganon_fastq_format_hip(ganon_ctx *ctx, int64_t n, const uint8_t *const *seq_buf,
+                                         const uint8_t *seq_sel, const int64_t *seq_nib_off, const int32_t *seq_len,
+                                         const uint8_t *reverse, const uint8_t *const *qual_buf,
+                                         const uint8_t *qual_sel, const int64_t *qual_off, const int32_t *qual_len,
+                                         const uint8_t *qual_rev, const char *names, const int64_t *name_off,
+                                         const int32_t *name_len, const uint8_t *mate, char *out, int64_t cap) {
+  return fq_one_shot(ctx, n, seq_buf, seq_sel, seq_nib_off, seq_len, reverse, qual_buf, qual_sel, qual_off, qual_len,
+                     qual_rev, names, name_off, name_len, mate, nullptr, nullptr, 0, out, cap);
+}
+
+GANON_API int64_t ganon_fastq_format_hip_mq(ganon_ctx *ctx, int64_t n, const uint8_t *const *seq_buf,
+                                            const uint8_t *seq_sel, const int64_t *seq_nib_off,
+                                            const int32_t *seq_len, const uint8_t *reverse,
+                                            const uint8_t *const *qual_buf, const uint8_t *qual_sel,
+                                            const int64_t *qual_off, const int32_t *qual_len, const uint8_t *qual_rev,
+                                            const char *names, const int64_t *name_off, const int32_t *name_len,
+                                            const uint8_t *mate, const uint8_t *orig_sel, const int64_t *orig_nib_off,
+                                            int32_t quality, char *out, int64_t cap) {
+  if (n > 0 && (!orig_sel || !orig_nib_off)) return GANON_FASTQ_FAILED;
+  return fq_one_shot(ctx, n, seq_buf, seq_sel, seq_nib_off, seq_len, reverse, qual_buf, qual_sel, qual_off, qual_len,
+                     qual_rev, names, name_off, name_len, mate, n ? orig_sel : nullptr, orig_nib_off, quality, out, cap);
 }

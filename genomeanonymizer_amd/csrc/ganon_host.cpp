@@ -1210,6 +1210,38 @@ GANON_HOST_API int64_t ganon_fastq_format(int64_t n, const uint8_t *const *seq_b
   return w;
 }
 
+// --masked_base_quality: the plain records, then every quality character that stands under a base
+// an SNV mask wrote (nibble of the masked copy != nibble of the read's original bases) set to
+// '!' + quality. The base at query position p is printed at text index p (forward) or L-1-p
+// (reverse), and that is the quality index patched, whatever order the qualities are printed in.
+GANON_HOST_API int64_t ganon_fastq_format_mq(int64_t n, const uint8_t *const *seq_buf, const uint8_t *seq_sel,
+                                             const int64_t *seq_nib_off, const int32_t *seq_len,
+                                             const uint8_t *reverse, const uint8_t *const *qual_buf,
+                                             const uint8_t *qual_sel, const int64_t *qual_off,
+                                             const int32_t *qual_len, const uint8_t *qual_rev,
+                                             const char *names, const int64_t *name_off, const int32_t *name_len,
+                                             const uint8_t *mate, const uint8_t *orig_sel,
+                                             const int64_t *orig_nib_off, int32_t quality, char *out, int64_t cap) {
+  if (n > 0 && (!orig_sel || !orig_nib_off || quality < 0 || quality > 93)) return INT64_MIN + 1;
+  const int64_t w = ganon_fastq_format(n, seq_buf, seq_sel, seq_nib_off, seq_len, reverse, qual_buf, qual_sel,
+                                       qual_off, qual_len, qual_rev, names, name_off, name_len, mate, out, cap);
+  if (w < 0) return w;
+  const char qc = (char)(33 + quality);
+  auto nib = [](const uint8_t *b, int64_t ni) -> int { return (ni & 1) ? (b[ni >> 1] & 0xF) : (b[ni >> 1] >> 4); };
+  int64_t o = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t L = seq_len[i], Q = qual_len[i], NL = name_len[i];
+    if (orig_sel[i] != 255 && Q == L) {
+      const uint8_t *mb = seq_buf[seq_sel[i]], *ob = seq_buf[orig_sel[i]];
+      char *q = out + o + NL + L + 7;
+      for (int32_t p = 0; p < L; ++p)
+        if (nib(mb, seq_nib_off[i] + p) != nib(ob, orig_nib_off[i] + p)) q[reverse[i] ? L - 1 - p : p] = qc;
+    }
+    o += 8 + (int64_t)NL + L + Q;
+  }
+  return w;
+}
+
 GANON_HOST_API void ganon_pack_nt16(const char *ascii, int64_t n, uint8_t *out) {
   int8_t lut[256];
   std::memset(lut, 15, sizeof lut);

@@ -108,6 +108,7 @@ struct State {
   bool reverse = false;
   std::string name;
   int mate = 1;
+  int mq = -1;               // --masked_base_quality: the quality put() writes beside the base (-1: off)
 
   void put(int64_t pos, uint8_t base) {   // np.put(..., mode='raise')
     const int64_t n = (int64_t)seq.size();
@@ -115,6 +116,13 @@ struct State {
       oraise(GANON_PLAN_E_INDEX, "index " + std::to_string(pos) + " is out of bounds for axis 0 with size " +
                                      std::to_string(n));
     seq[(size_t)(pos < 0 ? pos + n : pos)] = (char)base;
+    // mask_or_modify_base_pair's modify_qualities (AM:175-176): the forward qualities at the same
+    // index, so the character lands under the base as printed (a read without qualities has none)
+    if (mq >= 0 && has_qual) {
+      const int64_t nq = (int64_t)qual.size();
+      if (pos < -nq || pos >= nq) oraise(GANON_PLAN_E_INDEX, "array assignment index out of range");
+      qual[(size_t)(pos < 0 ? pos + nq : pos)] = (char)mq;
+    }
   }
   static std::string slice(const std::string &s, int64_t a, int64_t b) {   // python s[a:b], a, b >= 0
     const int64_t n = (int64_t)s.size();
@@ -238,6 +246,7 @@ struct ganon_objects {
   };
   std::map<IncKey, Plain> plain;                   // key (job, ds, row) with scope in IncKey.scope... see key
   std::unordered_map<int64_t, std::string> written;
+  int maskq = -1;                                  // ganon_objects_set_maskq
 
   static IncKey pkey(int64_t job, int64_t ds, int64_t scope, int64_t row) {
     return IncKey{(job << 2) | ds, row, scope};
@@ -255,6 +264,7 @@ struct ganon_objects {
     const Rec &cr = J.rec.at(key3(ds, c));
     const Rec &br = base >= 0 ? J.rec.at(key3(ds, base)) : cr;
     State st;
+    st.mq = maskq;
     st.seq = br.seq;
     st.has_qual = br.has_qual;
     st.qual = br.has_qual ? br.fwd_qual() : std::string();
@@ -327,6 +337,7 @@ struct ganon_objects {
 
   State plain_object(int64_t job, int64_t ds, int64_t scope, int64_t row, bool upd) {
     State st;
+    st.mq = maskq;
     auto it = plain.find(pkey(job, ds, scope, row));
     if (it == plain.end()) {
       st.has_seq = false;   // never written: it can only lend its flag / list
@@ -507,6 +518,12 @@ GANON_HOST_API int ganon_objects_create(ganon_objects **out) {
 }
 
 GANON_HOST_API void ganon_objects_free(ganon_objects *o) { delete o; }
+
+GANON_HOST_API int ganon_objects_set_maskq(ganon_objects *o, int32_t quality) {
+  if (!o || quality < -1 || quality > 93) return GANON_PLAN_E_ARG;
+  o->maskq = quality;
+  return GANON_PLAN_OK;
+}
 
 GANON_HOST_API int ganon_objects_add_job(ganon_objects *o, int32_t job, const uint8_t *blob, int64_t size) {
   if (!o || (size > 0 && !blob) || size < 0) return GANON_PLAN_E_ARG;

@@ -2,13 +2,16 @@
 
   python -m genomeanonymizer_amd.genome_anonymizer -d DIR -s samples.tsv -r ref.fa \\
       [-m complete_germline] [-c CPUS] [--record_statistics] [--enhanced_multiprocessing] [-v N]
-      [--compress_output]
+      [--compress_output] [--masked_base_quality Q]
 
 samples.tsv: tumor<TAB>normal<TAB>vcf per line, paths relative to DIR, '#' lines skipped.
 Outputs next to the inputs: re.sub('.bam|.sam|.cram', '.anonymized', path) + .1/.2.fastq
 (+ .single_end.fastq), and {normal_bam}.statistics.txt with --record_statistics.
 --compress_output (an extension: the reference writes plain FASTQ) writes .1/.2/.single_end.fastq.gz
 instead, BGZF members deflated on the GPU; GANON_COMPRESS_OUTPUT=1 is the same default.
+--masked_base_quality Q (an extension, 0..93; GANON_MASKED_BASE_QUALITY=Q is the same default): every
+base a germline SNV mask wrote is printed with quality chr(33 + Q), so that a caller run on the
+anonymized FASTQ does not read the synthetic base with the confidence of the one sequenced there.
 
 Multi-GPU: launch under ``torchrun --nproc-per-node N`` (or set WORLD_SIZE/RANK/LOCAL_RANK):
 contigs are sharded round-robin over the ranks; each rank decodes, masks and writes its own
@@ -52,6 +55,9 @@ def exec_parser(argv=None):
                         help="Accepted for compatibility; no effect (see SURVEY Q12)")
     parser.add_argument("--compress_output", action=BooleanOptionalAction,
                         help="Write BGZF-compressed .fastq.gz files, deflated on the GPU (default: GANON_COMPRESS_OUTPUT)")
+    parser.add_argument("--masked_base_quality", type=int, choices=range(0, 94), metavar="Q", default=None,
+                        help="Phred quality 0..93 printed under every base a germline SNV mask wrote "
+                             "(default: GANON_MASKED_BASE_QUALITY, else the qualities stay as they are)")
     parser.add_argument("-v", "--verbose", type=int, required=False, default=2, help="Verbosity of logging")
     parser.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     return parser.parse_args(argv)
@@ -87,6 +93,8 @@ def run_anonymizer(argv=None) -> None:
         sys.exit(1)
     if config.compress_output is not None:   # (the environment reaches spawned pair workers and every rank's paths)
         os.environ["GANON_COMPRESS_OUTPUT"] = "1" if config.compress_output else "0"
+    if config.masked_base_quality is not None:
+        os.environ["GANON_MASKED_BASE_QUALITY"] = str(config.masked_base_quality)
     vcfs, samples, outputs = read_samples(join_dir_file(config.directory, config.samples), config.directory)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))

@@ -200,6 +200,11 @@ def hip_lib():
     lib.ganon_fastq_format_hip.argtypes = [_p, C.c_int64, C.POINTER(_u8p), _u8p, _i64p, _i32p, _u8p,
                                            C.POINTER(_u8p), _u8p, _i64p, _i32p, _u8p, C.c_char_p, _i64p,
                                            _i32p, _u8p, C.c_char_p, C.c_int64]
+    lib.ganon_fastq_set_maskq.argtypes = [_p, _p, C.c_int64, _i32p, C.POINTER(_u8p), C.c_int32, _u8p, _i64p, C.c_int32]
+    lib.ganon_fastq_format_hip_mq.restype = C.c_int64
+    lib.ganon_fastq_format_hip_mq.argtypes = [_p, C.c_int64, C.POINTER(_u8p), _u8p, _i64p, _i32p, _u8p,
+                                              C.POINTER(_u8p), _u8p, _i64p, _i32p, _u8p, C.c_char_p, _i64p,
+                                              _i32p, _u8p, _u8p, _i64p, C.c_int32, C.c_char_p, C.c_int64]
     lib.ganon_indel_upload.argtypes = [_p, C.POINTER(GanonBatch), _p, C.POINTER(_p)]
     lib.ganon_indel_run.argtypes = [_p, _p]
     lib.ganon_indel_download.argtypes = [_p, _p, _p, C.c_int64]
@@ -248,6 +253,7 @@ EXPORTED_HIP_SYMBOLS = (
     "ganon_batch_path_counts", "ganon_batch_gated_runs",
     "ganon_fastq_upload", "ganon_fastq_run", "ganon_fastq_bytes", "ganon_fastq_device_output",
     "ganon_fastq_download", "ganon_fastq_free", "ganon_fastq_format_hip",
+    "ganon_fastq_set_maskq", "ganon_fastq_format_hip_mq",
     "ganon_indel_upload", "ganon_indel_run", "ganon_indel_download", "ganon_indel_info", "ganon_indel_free",
     "ganon_inflate", "ganon_inflate_hostcb", "ganon_inflate_device_output",
     "ganon_bam_columns", "ganon_bam_dcols_get", "ganon_bam_dcols_download", "ganon_bam_dcols_free",
@@ -256,13 +262,13 @@ EXPORTED_HIP_SYMBOLS = (
 )
 EXPORTED_HOST_SYMBOLS = (
     "ganon_bam_open", "ganon_bam_view_get", "ganon_bam_error", "ganon_bam_close",
-    "ganon_host_last_error", "ganon_host_inflate_backend", "ganon_fastq_format", "ganon_pack_nt16",
+    "ganon_host_last_error", "ganon_host_inflate_backend", "ganon_fastq_format", "ganon_fastq_format_mq", "ganon_pack_nt16",
     "ganon_plan_run", "ganon_plan_view_get", "ganon_plan_free", "ganon_plan_last_error", "ganon_io_replay",
     "ganon_bam_reader_open", "ganon_bam_reader_set_window", "ganon_bam_reader_has_index", "ganon_bam_reader_header",
     "ganon_bam_reader_contig", "ganon_bam_reader_region", "ganon_bam_reader_close",
     "ganon_resolver_create", "ganon_resolver_free", "ganon_resolver_contig", "ganon_resolver_pending",
     "ganon_resolver_finish", "ganon_resolver_take_log", "ganon_resolver_mark_written", "ganon_objects_pack", "ganon_blob_size", "ganon_blob_data",
-    "ganon_blob_free", "ganon_objects_create", "ganon_objects_free", "ganon_objects_add_job", "ganon_objects_add_plain",
+    "ganon_blob_free", "ganon_objects_create", "ganon_objects_free", "ganon_objects_set_maskq", "ganon_objects_add_job", "ganon_objects_add_plain",
     "ganon_objects_run", "ganon_objects_take", "ganon_objects_settle", "ganon_objects_last_error",
     "ganon_objects_take_all", "ganon_aux_sa_count", "ganon_fastq_edit", "ganon_gather_ranges", "ganon_gather_ranges2", "ganon_host_phase_times",
     "ganon_bam_reader_set_inflater", "ganon_bam_reader_set_buffer_alloc", "ganon_bam_reader_set_region_decoder",
@@ -437,6 +443,37 @@ def compress_output_default() -> bool:
     """``GANON_COMPRESS_OUTPUT=1``: BGZF-compressed FASTQ output (``--compress_output``) for library
     callers and for spawned pair workers and ranks."""
     return os.environ.get("GANON_COMPRESS_OUTPUT", "0") == "1"
+
+
+def masked_base_quality_default() -> Optional[int]:
+    """``GANON_MASKED_BASE_QUALITY=Q`` (0..93): the quality every base an SNV mask wrote is printed
+    with (``--masked_base_quality``), for library callers and for spawned pair workers and ranks. None
+    when unset or empty: the qualities are printed as they are."""
+    v = os.environ.get("GANON_MASKED_BASE_QUALITY", "").strip()
+    if not v:
+        return None
+    q = int(v)
+    if not 0 <= q <= 93:
+        raise GanonError(f"GANON_MASKED_BASE_QUALITY={v}: a phred quality 0..93")
+    return q
+
+
+def _maskq_args(recs: dict):
+    """(orig_sel, orig_nib_off, quality) of a record dict that asks for masked-base qualities and has at
+    least one original (``orig_sel`` uint8, 255 = none; ``orig_nib_off`` int64; ``maskq`` 0..93), else None:
+    the plain entry points run."""
+    q = recs.get("maskq")
+    if q is None:
+        return None
+    sel, off = recs["orig_sel"], recs["orig_nib_off"]
+    if sel.dtype != np.uint8 or off.dtype != np.int64 or not sel.flags["C_CONTIGUOUS"] or \
+            not off.flags["C_CONTIGUOUS"] or len(sel) != len(recs["seq_len"]) or len(off) != len(sel):
+        raise GanonError("FASTQ record arrays orig_sel / orig_nib_off must be C-contiguous uint8 / int64")
+    if not 0 <= int(q) <= 93:
+        raise GanonError("masked-base quality outside 0..93")
+    if not (sel != 255).any():
+        return None
+    return sel, off, int(q)
 
 
 def _as_stream(buffers) -> np.ndarray:
@@ -711,14 +748,36 @@ class HipMasker:
         return DeviceRef(self, h, len(a))
 
     # -- FASTQ formatter -------------------------------------------------------------------
+    formats_maskq = True    # format_fastq / format_fastq_batch honour a record dict's ``maskq`` (k_fq_maskq)
+
     def fastq_upload(self, recs: dict, seq_batch: "DeviceBatch" = None) -> "DeviceFastq":
         """Upload a record set (``fastq_records`` layout); with ``seq_batch`` the sequences are
         read from that device batch (buffer 0 = masked output, 1 = input) without a copy."""
         c, keep = _c_fastq_records(recs, seq_batch)
         h = _p()
         self._check(self._lib.ganon_fastq_upload(self._h, C.byref(c), C.byref(h)), "ganon_fastq_upload")
+        try:
+            self._set_maskq(h, recs, seq_batch is not None)
+        except GanonError:
+            self._lib.ganon_fastq_free(self._h, h)
+            raise
         del keep
         return DeviceFastq(self, h)
+
+    def _set_maskq(self, h, recs: dict, batch: bool) -> None:
+        """ganon_fastq_set_maskq when the record dict asks for masked-base qualities (``_maskq_args``)."""
+        mq = _maskq_args(recs)
+        if mq is None:
+            return
+        sel, off, q = mq
+        if batch:
+            bufs, nb = None, 0
+        else:
+            nb = len(recs["seq_bufs"])
+            bufs = (_u8p * nb)(*[b.ctypes.data_as(_u8p) for b in recs["seq_bufs"]])
+        self._check(self._lib.ganon_fastq_set_maskq(self._h, h, len(sel), recs["seq_len"].ctypes.data_as(_i32p), bufs, nb,
+                                                    sel.ctypes.data_as(_u8p), off.ctypes.data_as(_i64p), q),
+                    "ganon_fastq_set_maskq")
 
     def format_fastq_batch(self, recs: dict, gen: int) -> Optional[bytes]:
         """Format records whose sequences are in the last job batch (``recs`` as FastqFormatter
@@ -732,12 +791,17 @@ class HipMasker:
         sel = recs["seq_sel"]
         r["seq_nib_off"] = recs["seq_nib_off"] + np.where(sel == 2, 2 * int(recs["seq_base1"]), 0).astype(np.int64)
         r["seq_sel"] = np.minimum(sel, 1).astype(np.uint8)
+        if _maskq_args(recs) is not None:   # the originals: the batch's input, like every unmasked read
+            osel = recs["orig_sel"]
+            r["orig_nib_off"] = recs["orig_nib_off"] + np.where(osel == 2, 2 * int(recs["seq_base1"]), 0).astype(np.int64)
+            r["orig_sel"] = np.where(osel == 255, 255, np.minimum(osel, 1)).astype(np.uint8)
         t0 = time.perf_counter()
         c, keep = _c_fastq_records(r, seq_batch=db)
         h = _p()
         self._check(self._lib.ganon_fastq_upload(self._h, C.byref(c), C.byref(h)), "ganon_fastq_upload")
         del keep
         try:
+            self._set_maskq(h, r, True)
             t1 = time.perf_counter()
             self._check(self._lib.ganon_fastq_run(self._h, h), "ganon_fastq_run")
             n_bytes = int(self._lib.ganon_fastq_bytes(h))
@@ -760,7 +824,12 @@ class HipMasker:
         a = _fastq_args(recs)
         n_bytes = fastq_bytes(recs)
         out = _new_bytes(None, n_bytes)    # filled in place: no zero-fill, no copy out
-        w = self._lib.ganon_fastq_format_hip(self._h, *a, out, n_bytes)
+        mq = _maskq_args(recs)
+        if mq is None:
+            w = self._lib.ganon_fastq_format_hip(self._h, *a, out, n_bytes)
+        else:
+            w = self._lib.ganon_fastq_format_hip_mq(self._h, *a, mq[0].ctypes.data_as(_u8p), mq[1].ctypes.data_as(_i64p),
+                                                    mq[2], out, n_bytes)
         w = _fastq_result(w, lambda: self._lib.ganon_last_error(self._h).decode(errors="replace"))
         return out if w == n_bytes else out[:w]
 
@@ -856,7 +925,13 @@ def host_format_fastq(recs: dict) -> bytes:
     a = _fastq_args(recs)
     n_bytes = fastq_bytes(recs)
     out = _new_bytes(None, n_bytes)
-    w = _fastq_result(host_lib().ganon_fastq_format(*a, out, n_bytes), lambda: "host formatter")
+    mq = _maskq_args(recs)
+    if mq is None:
+        w = host_lib().ganon_fastq_format(*a, out, n_bytes)
+    else:
+        w = host_lib().ganon_fastq_format_mq(*a, mq[0].ctypes.data_as(_u8p), mq[1].ctypes.data_as(_i64p), mq[2], out,
+                                             n_bytes)
+    w = _fastq_result(w, lambda: "host formatter")
     return out if w == n_bytes else out[:w]
 
 
@@ -1495,12 +1570,15 @@ class ObjectStore:
     """``ganon_objects_*``: the content replay of the resolver log in libganon_host.so (objects.py
     restates it in Python)."""
 
-    def __init__(self):
+    def __init__(self, maskq: Optional[int] = None):
+        """``maskq``: --masked_base_quality (None: off), written wherever the replay writes a masked base."""
         self._lib = host_lib()
         h = _p()
         if self._lib.ganon_objects_create(C.byref(h)) != 0:
             raise GanonError("ganon_objects_create failed")
         self._h = h
+        if maskq is not None and self._lib.ganon_objects_set_maskq(h, int(maskq)) != 0:
+            raise GanonError("ganon_objects_set_maskq failed")
 
     def _check(self, rc: int) -> None:
         if rc == 0:
@@ -1610,6 +1688,10 @@ def host_lib():
     lib.ganon_fastq_format.argtypes = [C.c_int64, C.POINTER(_u8p), _u8p, _i64p, _i32p, _u8p, C.POINTER(_u8p),
                                        _u8p, _i64p, _i32p, _u8p, C.c_char_p, _i64p, _i32p, _u8p, C.c_char_p,
                                        C.c_int64]
+    lib.ganon_fastq_format_mq.restype = C.c_int64
+    lib.ganon_fastq_format_mq.argtypes = [C.c_int64, C.POINTER(_u8p), _u8p, _i64p, _i32p, _u8p, C.POINTER(_u8p),
+                                          _u8p, _i64p, _i32p, _u8p, C.c_char_p, _i64p, _i32p, _u8p, _u8p, _i64p,
+                                          C.c_int32, C.c_char_p, C.c_int64]
     lib.ganon_pack_nt16.argtypes = [C.c_char_p, C.c_int64, _u8p]
     lib.ganon_plan_run.argtypes = [C.POINTER(PlanInput), C.POINTER(_p)]
     lib.ganon_plan_view_get.argtypes = [_p, C.POINTER(PlanView)]
@@ -1628,6 +1710,7 @@ def host_lib():
     lib.ganon_blob_free.argtypes = [_p]
     lib.ganon_objects_create.argtypes = [C.POINTER(_p)]
     lib.ganon_objects_free.argtypes = [_p]
+    lib.ganon_objects_set_maskq.argtypes = [_p, C.c_int32]
     lib.ganon_objects_add_job.argtypes = [_p, C.c_int32, C.c_char_p, C.c_int64]
     lib.ganon_objects_add_plain.argtypes = [_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_char_p,
                                             C.c_int64, C.c_int64, _i64p, _p, _i64p, _i32p]

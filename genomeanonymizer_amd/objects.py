@@ -121,10 +121,11 @@ def mask_diffs(rec: Record, masked: bytes) -> List[Tuple[int, int, int, int]]:
 
 class State:
     """One AnonymizedRead's mutable content."""
-    __slots__ = ("seq", "qual", "left", "flag", "reverse", "name", "mate")
+    __slots__ = ("seq", "qual", "left", "flag", "reverse", "name", "mate", "mq")
 
-    def __init__(self, seq: bytearray, qual, reverse: bool, name: bytes, mate: int):
+    def __init__(self, seq: bytearray, qual, reverse: bool, name: bytes, mate: int, mq: Optional[int] = None):
         self.seq, self.qual, self.reverse, self.name, self.mate = seq, qual, reverse, name, mate
+        self.mq = mq          # --masked_base_quality: the quality put() writes beside the base (None: off)
         self.left: list = []
         self.flag = False
 
@@ -134,6 +135,13 @@ class State:
         if not -n <= pos < n:
             raise IndexError(f"index {pos} is out of bounds for axis 0 with size {n}")
         self.seq[pos] = base
+        if self.mq is not None and self.qual is not None:
+            # modify_qualities of the same call (AM:175-176): the forward qualities at the same index
+            q = bytearray(self.qual)
+            if not -len(q) <= pos < len(q):
+                raise IndexError("array assignment index out of range")
+            q[pos] = self.mq
+            self.qual = bytes(q)
 
     def apply(self) -> None:
         """mask_or_anonymize_left_over_variants when flagged (AM:254-270)."""
@@ -195,6 +203,8 @@ class Replay:
         self.jobs: Dict[int, dict] = {}
         self.states: Dict[int, State] = {}
         self.written: Dict[int, bytes] = {}
+        from . import native
+        self.maskq = native.masked_base_quality_default()
 
     def add_job(self, job: int, cx: Optional[dict]) -> None:
         if cx is not None and len(cx["objs"]):
@@ -218,7 +228,7 @@ class Replay:
         crec = cx["rec"][(ds, c)]
         brec = cx["rec"][(ds, base)] if base >= 0 else crec
         q = brec.forward_qual()
-        st = State(bytearray(brec.seq), q, crec.reverse, crec.name, 1 if crec.flag & 0x40 else 2)
+        st = State(bytearray(brec.seq), q, crec.reverse, crec.name, 1 if crec.flag & 0x40 else 2, self.maskq)
         if scope < 0:
             return st
         lo = brec.pos if base >= 0 else None
@@ -248,12 +258,12 @@ class Replay:
         rec = self.carry.get((job, ds, scope, row, 2 if edits else 0))
         if rec is None:
             # not carried: only a copy no write can name (fastq() refuses it)
-            st = State(None, None, False, b"", 0)
+            st = State(None, None, False, b"", 0, self.maskq)
         else:
             flag = self.carry_info[(job, ds, row)]
             rev = bool(flag & 0x10)
             name, seq, mate, qual = decode_fastq(rec, rev)
-            st = State(bytearray(seq), qual[::-1] if rev else qual, rev, name, mate)
+            st = State(bytearray(seq), qual[::-1] if rev else qual, rev, name, mate, self.maskq)
         st.left = [(call.variant_type, irp, call) for irp, call in edits]
         st.flag = bool(st.left)
         if scope >= 0:
@@ -313,7 +323,7 @@ class NativeReplay:
     def __init__(self, carry: dict, carry_info: dict):
         from . import native
         self.carry, self.carry_info = carry, carry_info
-        self.store = native.ObjectStore()
+        self.store = native.ObjectStore(native.masked_base_quality_default())
         self.written: Dict[int, bytes] = {}
 
     def add_job(self, job: int, cx: Optional[bytes]) -> None:

@@ -7,7 +7,9 @@
   and the qualities printed in the BAM's stored order for every read (they are
   loaded forward-oriented and reversed once more on output). Bulk formatting runs on the
   GPU (``ganon_fastq_format_hip`` through the masking engine) or in libganon_host.so; the
-  rare indel-edited records get their left-overs applied by ``native.fastq_edit``.
+  rare indel-edited records get their left-overs applied by ``native.fastq_edit``. With
+  ``--masked_base_quality Q`` (``GANON_MASKED_BASE_QUALITY``) the records name their original bases
+  and the formatter prints every base an SNV mask wrote with quality Q.
 * the statistics file of ``AnonymizedVariantsStatistics.write_statistics`` (SR:175-242).
 """
 from __future__ import annotations
@@ -50,6 +52,7 @@ class FastqFormatter:
         self.res = res
         self.backend = backend or native.host_format_fastq
         self.device_backend = device_backend
+        self.maskq = native.masked_base_quality_default()   # --masked_base_quality (None: off)
         self._qual_bufs = [tables[0].qual, tables[1].qual]
         self._names = np.concatenate([np.asarray(tables[0].names_blob, np.uint8), np.asarray(tables[1].names_blob, np.uint8)])
         self._name_base = (0, len(tables[0].names_blob))
@@ -92,7 +95,12 @@ class FastqFormatter:
         seq_len = pick("l_seq", np.int32)
         flag = pick("flag", np.int64)
         name_off = pick("name_off", np.int64) + np.where(t0, self._name_base[0], self._name_base[1])
+        mq = {}
+        if self.maskq is not None:   # a masked copy's original: the read's own bases in its BAM's buffer
+            mq = {"maskq": self.maskq, "orig_sel": np.where(sc >= 0, 1 + ds, 255).astype(np.uint8),
+                  "orig_nib_off": (2 * seq_off_t).astype(np.int64)}
         return {
+            **mq,
             "seq_bufs": self._seq_bufs(bool((seq_sel == 0).any())) if seq_bufs else None, "seq_sel": seq_sel,
             "seq_nib_off": (2 * byte_off).astype(np.int64),
             "seq_len": seq_len, "reverse": pick("is_reverse", np.uint8),

@@ -310,6 +310,32 @@ GANON_API int64_t ganon_fastq_format_hip(ganon_ctx *ctx, int64_t n, const uint8_
                                          const uint8_t *qual_rev, const char *names,
                                          const int64_t *name_off, const int32_t *name_len,
                                          const uint8_t *mate, char *out, int64_t cap);
+/* --masked_base_quality (additive; the ABI version stays 5). Between ganon_fastq_upload and
+ * ganon_fastq_run: record i's original bases are seq_len[i] nibbles from nibble orig_nib_off[i] of
+ * original buffer orig_sel[i] (255: the record has none). After the formatter, ganon_fastq_run then
+ * launches k_fq_maskq over its output: wherever a nibble of the record's sequence differs from the
+ * original's (an SNV mask wrote the reference base there), the quality character under that base as
+ * printed — text index p, or seq_len[i] - 1 - p when reverse[i] — becomes '!' + quality (0..93).
+ * Records with qual_len != seq_len or without an original are left alone; without any original
+ * nothing is launched. n and seq_len are the uploaded records' (checked). Records uploaded with a
+ * seq_batch: orig_buf is ignored, selector 0 / 1 = the batch's masked output / input. Host
+ * buffers: selectors index orig_buf (n_orig_bufs <= GANON_FASTQ_MAX_BUFS entries, normally the
+ * seq_buf array of the upload), whose used slices are uploaded here. Synchronous. */
+GANON_API int ganon_fastq_set_maskq(ganon_ctx *ctx, ganon_fastq *f, int64_t n, const int32_t *seq_len,
+                                    const uint8_t *const *orig_buf, int32_t n_orig_bufs,
+                                    const uint8_t *orig_sel, const int64_t *orig_nib_off, int32_t quality);
+/* One-shot with exactly the arguments of the host formatter ganon_fastq_format_mq
+ * (include/ganon_host.h; the originals are buffers of seq_buf) and the same bytes. */
+GANON_API int64_t ganon_fastq_format_hip_mq(ganon_ctx *ctx, int64_t n, const uint8_t *const *seq_buf,
+                                            const uint8_t *seq_sel, const int64_t *seq_nib_off,
+                                            const int32_t *seq_len, const uint8_t *reverse,
+                                            const uint8_t *const *qual_buf, const uint8_t *qual_sel,
+                                            const int64_t *qual_off, const int32_t *qual_len,
+                                            const uint8_t *qual_rev, const char *names,
+                                            const int64_t *name_off, const int32_t *name_len,
+                                            const uint8_t *mate, const uint8_t *orig_sel,
+                                            const int64_t *orig_nib_off, int32_t quality, char *out,
+                                            int64_t cap);
 
 /* ---- Germline indel tally ----------------------------------------------
  * Replaces, for every scope of an uploaded batch at once, process_indels

@@ -134,6 +134,22 @@ GANON_HOST_API int64_t ganon_fastq_format(int64_t n, const uint8_t *const *seq_b
                                           const int32_t *qual_len, const uint8_t *qual_rev,
                                           const char *names, const int64_t *name_off, const int32_t *name_len,
                                           const uint8_t *mate, char *out, int64_t cap);
+/* --masked_base_quality: ganon_fastq_format, then in every record with orig_sel[i] != 255 and
+ * qual_len[i] == seq_len[i] the quality character under every base an SNV mask wrote becomes
+ * '!' + quality (0..93). A base is masked iff nibble seq_nib_off[i] + p of seq_buf[seq_sel[i]]
+ * differs from nibble orig_nib_off[i] + p of seq_buf[orig_sel[i]] (the read's original bases); it
+ * is printed at text index p, or seq_len[i] - 1 - p when reverse[i], and that index of the quality
+ * line is the one patched. orig_sel all 255 gives ganon_fastq_format's bytes. Same return
+ * convention; INT64_MIN + 1 for a null array or a quality out of range. Byte-identical to
+ * ganon_fastq_format_hip_mq (include/ganon.h). */
+GANON_HOST_API int64_t ganon_fastq_format_mq(int64_t n, const uint8_t *const *seq_buf, const uint8_t *seq_sel,
+                                             const int64_t *seq_nib_off, const int32_t *seq_len,
+                                             const uint8_t *reverse, const uint8_t *const *qual_buf,
+                                             const uint8_t *qual_sel, const int64_t *qual_off,
+                                             const int32_t *qual_len, const uint8_t *qual_rev,
+                                             const char *names, const int64_t *name_off, const int32_t *name_len,
+                                             const uint8_t *mate, const uint8_t *orig_sel,
+                                             const int64_t *orig_nib_off, int32_t quality, char *out, int64_t cap);
 
 /* Indel left-overs applied to formatted records (replaces the per-record host loop of
  * AnonymizedRead.mask_or_anonymize_left_over_variants, anonymizer_methods.py:254-270, and
@@ -397,6 +413,11 @@ GANON_HOST_API void ganon_blob_free(ganon_blob *b);
 typedef struct ganon_objects ganon_objects;
 GANON_HOST_API int ganon_objects_create(ganon_objects **out);
 GANON_HOST_API void ganon_objects_free(ganon_objects *o);
+/* --masked_base_quality: objects created from now on write `quality` (0..93; -1 off, the default) into
+ * their forward qualities wherever they write a masked base (mask_or_modify_base_pair's
+ * modify_qualities, anonymizer_methods.py:170-176): directly or as an SNV left-over. A read without
+ * qualities keeps none. */
+GANON_HOST_API int ganon_objects_set_maskq(ganon_objects *o, int32_t quality);
 /* a packed job (its object ids are job << 32 | index) */
 GANON_HOST_API int ganon_objects_add_job(ganon_objects *o, int32_t job, const uint8_t *blob, int64_t size);
 /* a plain instance's content for log entries 1 / 4: its formatted record (writer.py), BAM flag and

@@ -19,6 +19,8 @@ Prints one JSON line with per-stage seconds, reads/s, bases/s and the process's 
                              # host decode threads 16 / P each); wall = the slowest rank's
     GANON_COMPRESS_OUTPUT=1  # BGZF-compressed .fastq.gz output, deflated on the GPU: the same
                              # line with "compress_output": true, for the price of the flag
+    GANON_MASKED_BASE_QUALITY=Q  # --masked_base_quality: masked bases printed with quality Q: the
+                             # same line with "masked_base_quality": Q
     E2E_DISK_PROBE=1 ...     # also time 2 GiB of pwrite into OUTDIR (4 files at once, as the product
                              # writes; page cache, then with fsync): the box's write bandwidth
 """
@@ -211,6 +213,7 @@ def main():
                      "cpu_s": round(best["cpu_s"], 2), "cores_busy": round(best["cpu_s"] / best["wall_s"], 2),
                      "cpu_us_per_read": round(best["cpu_s"] / max(1, best["reads"]) * 1e6, 3),
                      "compress_output": bool(gz),
+                     "masked_base_quality": _native.masked_base_quality_default(),
                      "cpus_available": len(os.sched_getaffinity(0)),
                      "output_bytes": sum(os.path.getsize(os.path.join(out, f"{x}_{mode}{s}{gz}"))
                                          for x in ("tumor", "normal") for s in (".1.fastq", ".2.fastq"))}

@@ -26,6 +26,13 @@
 // scalar columns, the wave copies name / CIGAR / sequence / quality / aux bytes lane-strided and sums
 // the reference length of its CIGAR ops for bam_endpos. Bytes are copied as bytes: BAM fields are
 // not aligned in the stream.
+//
+// Hashed names (--hash_read_names, ganon_ctx_set_name_key). With a key on the context every name takes
+// 33 bytes (32 hex characters of its keyed BLAKE2s-128, ganon_name_hash.h, and a NUL), the scatter
+// copies no name bytes, and k_bam_name_hash, a thread per record, reads each name from the stream and
+// writes the name blob: a workgroup's 256 names are one contiguous 8,448-byte range, built in LDS and
+// stored as coalesced dwords. Without a key nothing of this runs: the sizes and scatter kernels are
+// the instantiations they were.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
@@ -275,6 +282,8 @@ struct Sizes {
 };
 
 // Per record: the blob bytes it takes (records_to_columns' first pass), or the first bad record.
+// Hashed: every name takes ganon_nh::kSlot bytes.
+template <bool Hashed>
 __global__ void __launch_bounds__(kBamThreads) k_bam_sizes(const uint8_t *__restrict__ d, const int64_t *__restrict__ rec,
                                                            int64_t nr, Sizes S, unsigned long long *__restrict__ first_bad) {
   const int64_t i = (int64_t)blockIdx.x * kBamThreads + threadIdx.x;
@@ -291,7 +300,7 @@ __global__ void __launch_bounds__(kBamThreads) k_bam_sizes(const uint8_t *__rest
     S.name[i] = S.cig[i] = S.seq[i] = S.qual[i] = S.aux[i] = 0;
     return;
   }
-  S.name[i] = l_rn + ((l_rn == 0 || r[32 + l_rn - 1] != 0) ? 1 : 0);
+  S.name[i] = Hashed ? ganon_nh::kSlot : l_rn + ((l_rn == 0 || r[32 + l_rn - 1] != 0) ? 1 : 0);
   S.cig[i] = ncig;
   S.seq[i] = ((int64_t)lseq + 1) / 2;
   S.qual[i] = lseq;
@@ -314,7 +323,8 @@ namespace {
 
 // Record i's columns and blob bytes, by one wave; src(k) = byte k of the record (its block_size
 // field first), from global memory or from the block's LDS copy.
-template <class Src>
+// Hashed: the name bytes are k_bam_name_hash's (none copied here), name_len = 32.
+template <bool Hashed, class Src>
 __device__ __forceinline__ void scatter_record(const ganon_bam_cols &V, int64_t i, int lane, Src src) {
   uint8_t *cig8 = reinterpret_cast<uint8_t *>(V.cigar);
   const int hb = lane < 36 ? (int)src(lane) : 0;   // block_size + the fixed fields
@@ -347,13 +357,13 @@ __device__ __forceinline__ void scatter_record(const ganon_bam_cols &V, int64_t 
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int k = k0 + 64 * u + lane;
-      if (k < body) {
+      if (k < body && !(Hashed && k < e_name)) {
         uint8_t *base = k < e_name ? d_name : k < e_cig ? d_cig : k < e_seq ? d_seq : k < e_qual ? d_qual : d_aux;
         base[k] = v[u];
       }
     }
   }
-  if (lane == 0 && V.name_off[i + 1] - o_name > l_rn) V.names[o_name + l_rn] = 0;   // (a name without its NUL)
+  if (!Hashed && lane == 0 && V.name_off[i + 1] - o_name > l_rn) V.names[o_name + l_rn] = 0;   // (a name without its NUL)
   // the reference length of the M / D / N / = / X ops (bam_endpos)
   unsigned long long rl = 0;
   for (int k = lane; k < ncig; k += 64) {
@@ -378,7 +388,7 @@ __device__ __forceinline__ void scatter_record(const ganon_bam_cols &V, int64_t 
     V.mate_tid[i] = (int32_t)w32(24);
     V.mate_pos[i] = (int32_t)w32(28);
     V.tlen[i] = (int32_t)w32(32);
-    V.name_len[i] = l_rn > 0 ? l_rn - 1 : 0;
+    V.name_len[i] = Hashed ? ganon_nh::kHexLen : (l_rn > 0 ? l_rn - 1 : 0);
     V.aux_len[i] = (int32_t)na;
   }
 }
@@ -396,6 +406,7 @@ constexpr int kStage = GANON_SCAT_STAGE;      // LDS bytes staged per workgroup
 // copied to LDS with coalesced aligned dword loads, then each wave reads its record's bytes from
 // there (a byte per lane per instruction from global memory, BAM fields being unaligned, cost the
 // texture path as much as the stores); a run longer than the LDS copy reads global memory.
+template <bool Hashed>
 __global__ void __launch_bounds__(kBamThreads) k_bam_scatter(const uint8_t *__restrict__ d, int64_t n,
                                                              const int64_t *__restrict__ rec, int64_t nr,
                                                              ganon_bam_cols V) {
@@ -428,11 +439,60 @@ __global__ void __launch_bounds__(kBamThreads) k_bam_scatter(const uint8_t *__re
     const int64_t o = rec[i];
     if (fits) {
       const int base = (int)(o - a0);
-      scatter_record(V, i, lane, [&](int64_t k) { return sb[base + k]; });
+      scatter_record<Hashed>(V, i, lane, [&](int64_t k) { return sb[base + k]; });
     } else {
-      scatter_record(V, i, lane, [&](int64_t k) { return d[o + k]; });
+      scatter_record<Hashed>(V, i, lane, [&](int64_t k) { return d[o + k]; });
     }
   }
+}
+
+// The name blob of hashed names, a thread per record: record i's name (the bytes the unhashed columns
+// report: l_read_name - 1 of them from byte 36 of the record, its fields checked by k_bam_sizes) to
+// 32 hex characters and a NUL at names[33 i]. The workgroup's kBamThreads slots are contiguous and
+// start at a multiple of 4 bytes (33 * 256 i0; the blob is 256-byte aligned): they are built in LDS
+// and stored as dwords, the last workgroup's odd tail as bytes.
+__global__ void __launch_bounds__(kBamThreads) k_bam_name_hash(const uint8_t *__restrict__ d, int64_t n,
+                                                               const int64_t *__restrict__ rec, int64_t nr,
+                                                               ganon_nh::KeyState ks, char *__restrict__ names) {
+  __shared__ uint32_t slots[kBamThreads * ganon_nh::kSlot / 4];
+  uint8_t *sb = reinterpret_cast<uint8_t *>(slots);
+  const int64_t i0 = (int64_t)blockIdx.x * kBamThreads;
+  const int64_t i = i0 + threadIdx.x;
+  if (i < nr) {
+    const int64_t o = rec[i];
+    const int l_rn = d[o + 12];
+    const uint8_t *nm = d + o + 36;
+    const int64_t left = n - (o + 36);   // stream bytes from the name's first on (>= l_rn)
+    uint8_t *slot = sb + ganon_nh::kSlot * threadIdx.x;
+    ganon_nh::hash_name(
+        ks, l_rn > 0 ? l_rn - 1 : 0,
+        [&](int k, int nb) {
+          // the two aligned dwords that hold name bytes k .. k + 3 when the stream has them, else bytes
+          const uintptr_t a = reinterpret_cast<uintptr_t>(nm + k);
+          const int64_t pre = (int64_t)(a & 3);
+          if (nb == 4 && k + 8 - pre <= left) {
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(a - pre);
+            return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)pre);
+          }
+          uint32_t v = 0;
+          for (int c = 0; c < nb; ++c) v |= (uint32_t)nm[k + c] << (8 * c);
+          return v;
+        },
+        [&](int k, uint32_t w) {
+          slot[4 * k] = (uint8_t)w;
+          slot[4 * k + 1] = (uint8_t)(w >> 8);
+          slot[4 * k + 2] = (uint8_t)(w >> 16);
+          slot[4 * k + 3] = (uint8_t)(w >> 24);
+        });
+    slot[ganon_nh::kHexLen] = 0;
+  }
+  __syncthreads();
+  const int cnt = (int)min((int64_t)kBamThreads, nr - i0);
+  const int bytes = cnt * ganon_nh::kSlot;
+  char *out = names + ganon_nh::kSlot * i0;
+  uint32_t *out4 = reinterpret_cast<uint32_t *>(out);
+  for (int w = threadIdx.x; w < bytes / 4; w += kBamThreads) out4[w] = slots[w];
+  if ((int)threadIdx.x < (bytes & 3)) out[(bytes & ~3) + threadIdx.x] = (char)sb[(bytes & ~3) + threadIdx.x];
 }
 
 unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBamThreads - 1) / kBamThreads); }
@@ -630,7 +690,10 @@ int columns(ganon_ctx *ctx, const uint8_t *d, int64_t p, int64_t n, ganon_bam_dc
     for (int64_t *z : {S.name, S.cig, S.seq, S.qual, S.aux}) HIP_OR_FAIL(hipMemsetAsync(z + nr, 0, 8, s));
     if (nr) {
       ganon_detail::KernelScope ks(ctx, "k_bam_sizes");
-      hipLaunchKernelGGL(k_bam_sizes, dim3(grid_of(nr)), dim3(kBamThreads), 0, s, d, V.rec_off, nr, S, first_bad);
+      if (ctx->name_hash)
+        hipLaunchKernelGGL(k_bam_sizes<true>, dim3(grid_of(nr)), dim3(kBamThreads), 0, s, d, V.rec_off, nr, S, first_bad);
+      else
+        hipLaunchKernelGGL(k_bam_sizes<false>, dim3(grid_of(nr)), dim3(kBamThreads), 0, s, d, V.rec_off, nr, S, first_bad);
     }
     if ((rc = check_launch(ctx, "k_bam_sizes"))) return rc;
     size_t tb = 0;
@@ -679,9 +742,20 @@ int columns(ganon_ctx *ctx, const uint8_t *d, int64_t p, int64_t n, ganon_bam_dc
   if (nr) {
     ganon_detail::KernelScope ks(ctx, "k_bam_scatter");
     const unsigned grid = (unsigned)((nr + kScatRecs - 1) / kScatRecs);
-    hipLaunchKernelGGL(k_bam_scatter, dim3(grid), dim3(kBamThreads), 0, s, d, n, V.rec_off, nr, V);
+    if (ctx->name_hash)
+      hipLaunchKernelGGL(k_bam_scatter<true>, dim3(grid), dim3(kBamThreads), 0, s, d, n, V.rec_off, nr, V);
+    else
+      hipLaunchKernelGGL(k_bam_scatter<false>, dim3(grid), dim3(kBamThreads), 0, s, d, n, V.rec_off, nr, V);
   }
   if ((rc = check_launch(ctx, "k_bam_scatter"))) return rc;
+  if (nr && ctx->name_hash) {   // (names_bytes = 33 nr: k_bam_sizes<true>)
+    {
+      ganon_detail::KernelScope ks(ctx, "k_bam_name_hash");
+      hipLaunchKernelGGL(k_bam_name_hash, dim3(grid_of(nr)), dim3(kBamThreads), 0, s, d, n, V.rec_off, nr, ctx->name_key,
+                         V.names);
+    }
+    if ((rc = check_launch(ctx, "k_bam_name_hash"))) return rc;
+  }
   return ganon_batch_sync(ctx);   // (collects the kernel times when profiling)
 }
 
@@ -734,6 +808,15 @@ GANON_API int ganon_bam_columns(ganon_ctx *ctx, const uint8_t *stream, int64_t p
     return rc;
   }
   *out = H;
+  return GANON_OK;
+}
+
+GANON_API int ganon_ctx_set_name_key(ganon_ctx *ctx, const uint8_t *key, int32_t key_len) {
+  if (!ctx) return GANON_E_ARG;
+  if (key_len < 0 || key_len > ganon_nh::kMaxKey || (key_len > 0 && !key))
+    return fail(ctx, GANON_E_ARG, "ganon_ctx_set_name_key: a key of 1..32 bytes, or length 0 for none");
+  ctx->name_hash = key_len > 0;
+  if (ctx->name_hash) ganon_nh::key_state(key, key_len, &ctx->name_key);
   return GANON_OK;
 }
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/ganon.h"
+#include "ganon_name_hash.h"
 
 struct ganon_inflate_state;                       // ganon_inflate.hip: grow-only device buffers
 void ganon_inflate_free(ganon_inflate_state *st);
@@ -67,6 +68,8 @@ struct ganon_ctx {
   size_t dcache_bytes = 0;
   ganon_inflate_state *inflate = nullptr;   // BGZF inflate buffers (first ganon_inflate)
   ganon_deflate_state *deflate = nullptr;   // BGZF deflate buffers (first ganon_deflate_bgzf)
+  bool name_hash = false;                   // ganon_ctx_set_name_key: the BAM decoder hashes the read names
+  ganon_nh::KeyState name_key{};
   // GANON_INDEL_FORK=1: the indel tally of a batch runs on a side stream forked after the batch's
   // prep (fork_ev, recorded by ganon_batch_run before the group kernel) and joined back (join_ev), so
   // that its latency-bound launches overlap the bandwidth-bound group kernel (they read only the

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/ganon_host.h"
+#include "ganon_name_hash.h"
 
 namespace {
 
@@ -282,8 +283,10 @@ int parse_header(const uint8_t *d, int64_t n, ganon_bam *bam, int64_t &p) {
 // Column arrays of the records packed back to back in d[p, n) (each: block_size + body), or, with
 // `known`, of the records at those offsets of d (the reader's scans walked and checked them already:
 // their records stay in place in the scan's buffer, no boundary walk and no copy of the kept runs).
+// With ks (--hash_read_names) every name is replaced, here where it enters the table, by its keyed
+// hash: 32 hex characters and a NUL, name_off[i] = 33 i; the hash runs on the name pass's threads.
 int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, int threads,
-                       const std::vector<int64_t> *known = nullptr) {
+                       const std::vector<int64_t> *known = nullptr, const ganon_nh::KeyState *ks = nullptr) {
   const int nt = std::max(1, std::min(threads, 64));
   // ---- records: boundaries (sequential), sizes + offsets, then columns in parallel ----
   std::vector<int64_t> own;   // offset of each record's block_size field
@@ -328,7 +331,7 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
         o_name[i + 1] = o_cig[i + 1] = o_seq[i + 1] = o_qual[i + 1] = o_aux[i + 1] = 0;
         continue;
       }
-      o_name[i + 1] = l_rn + ((l_rn == 0 || r[32 + l_rn - 1] != 0) ? 1 : 0);
+      o_name[i + 1] = ks ? ganon_nh::kSlot : l_rn + ((l_rn == 0 || r[32 + l_rn - 1] != 0) ? 1 : 0);
       o_cig[i + 1] = ncig;
       o_seq[i + 1] = (lseq + 1) / 2;
       o_qual[i + 1] = lseq;
@@ -379,10 +382,16 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
       bam->tlen[i] = rtlen;
       int64_t q = 32;
       bam->name_off[i] = o_name[i];
-      bam->name_len[i] = l_rn > 0 ? l_rn - 1 : 0;
       char *nm = bam->names.data() + o_name[i];
-      copy_bytes(nm, r + q, l_rn);
-      if (o_name[i + 1] - o_name[i] > l_rn) nm[l_rn] = '\0';
+      if (ks) {   // (the bytes the unkeyed table reports as the name: l_rn - 1 of them, NUL or not)
+        bam->name_len[i] = ganon_nh::kHexLen;
+        ganon_nh::hash_bytes(*ks, r + q, l_rn > 0 ? l_rn - 1 : 0, nm);
+        nm[ganon_nh::kHexLen] = '\0';
+      } else {
+        bam->name_len[i] = l_rn > 0 ? l_rn - 1 : 0;
+        copy_bytes(nm, r + q, l_rn);
+        if (o_name[i + 1] - o_name[i] > l_rn) nm[l_rn] = '\0';
+      }
       q += l_rn;
       bam->cig_off[i] = o_cig[i];
       int64_t rlen = 0;
@@ -414,7 +423,7 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
 
 }  // namespace
 
-static int bam_open_impl(const char *path, int threads, ganon_bam **out) {
+static int bam_open_impl(const char *path, int threads, ganon_bam **out, const ganon_nh::KeyState *ks = nullptr) {
   FILE *fh = std::fopen(path, "rb");
   if (!fh) return set_err(std::string("cannot open ") + path);
   std::fseek(fh, 0, SEEK_END);
@@ -451,7 +460,7 @@ static int bam_open_impl(const char *path, int threads, ganon_bam **out) {
     delete bam;
     return hr < 0 ? -1 : set_err("truncated header");
   }
-  if (records_to_columns(data.data(), p, (int64_t)data.size(), bam, threads) != 0) {
+  if (records_to_columns(data.data(), p, (int64_t)data.size(), bam, threads, nullptr, ks) != 0) {
     delete bam;
     return -1;
   }
@@ -471,6 +480,51 @@ GANON_HOST_API int ganon_bam_open(const char *path, int threads, ganon_bam **out
   } catch (const std::exception &e) {
     return set_err(std::string("BAM decode failed: ") + e.what());
   }
+}
+
+GANON_HOST_API int ganon_bam_open_keyed(const char *path, int threads, const uint8_t *key, int32_t key_len,
+                                        ganon_bam **out) {
+  if (!path || !out) return set_err("null argument");
+  *out = nullptr;
+  if (!key || key_len < 1 || key_len > ganon_nh::kMaxKey) return set_err("ganon_bam_open_keyed: a key of 1..32 bytes");
+  ganon_nh::KeyState ks;
+  ganon_nh::key_state(key, key_len, &ks);
+  try {
+    return bam_open_impl(path, threads, out, &ks);
+  } catch (const std::bad_alloc &) {
+    return set_err("out of memory decoding the BAM file");
+  } catch (const std::exception &e) {
+    return set_err(std::string("BAM decode failed: ") + e.what());
+  }
+}
+
+GANON_HOST_API int ganon_names_hash(const char *names, const int64_t *off, const int32_t *len, int64_t n,
+                                    const uint8_t *key, int32_t key_len, int threads, char *out) {
+  if (n < 0 || (n > 0 && (!off || !len || !out)) || !key || key_len < 1 || key_len > ganon_nh::kMaxKey)
+    return set_err("ganon_names_hash: bad arguments");
+  for (int64_t i = 0; i < n; ++i)
+    if (len[i] < 0 || len[i] > 255 || off[i] < 0 || (len[i] > 0 && !names))
+      return set_err("ganon_names_hash: a name of 0..255 bytes at an offset >= 0");
+  ganon_nh::KeyState ks;
+  ganon_nh::key_state(key, key_len, &ks);
+  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)threads, 64, n}));
+  const int64_t per = (n + nt - 1) / nt;
+  auto run = [&](int64_t i0, int64_t i1) {
+    for (int64_t i = i0; i < i1; ++i) {
+      char *o = out + ganon_nh::kSlot * i;
+      ganon_nh::hash_bytes(ks, reinterpret_cast<const uint8_t *>(names) + off[i], len[i], o);
+      o[ganon_nh::kHexLen] = '\0';
+    }
+  };
+  try {
+    std::vector<std::thread> ts;
+    for (int t = 1; t < nt; ++t) ts.emplace_back(run, std::min(n, t * per), std::min(n, (t + 1) * per));
+    run(0, std::min(n, per));
+    for (auto &th : ts) th.join();
+  } catch (const std::exception &e) {
+    return set_err(std::string("ganon_names_hash: ") + e.what());
+  }
+  return 0;
 }
 
 GANON_HOST_API int ganon_bam_view_get(ganon_bam *b, ganon_bam_view *v) {
@@ -556,6 +610,8 @@ struct ganon_bam_reader {
   void *rdec_user = nullptr;             // window decoded whole by it (at least rdec_min blocks)
   int64_t rdec_min = 64;
   ganon_buf_free_fn rdec_release = nullptr;
+  bool hashed = false;                   // ganon_bam_reader_set_name_key: names enter the tables hashed
+  ganon_nh::KeyState name_key{};
 };
 
 namespace {
@@ -1033,6 +1089,14 @@ GANON_HOST_API int ganon_bam_reader_set_region_decoder(ganon_bam_reader *R, gano
   return 0;
 }
 
+GANON_HOST_API int ganon_bam_reader_set_name_key(ganon_bam_reader *R, const uint8_t *key, int32_t key_len) {
+  if (!R || key_len < 0 || key_len > ganon_nh::kMaxKey || (key_len > 0 && !key))
+    return set_err("ganon_bam_reader_set_name_key: a key of 1..32 bytes, or length 0 for none");
+  R->hashed = key_len > 0;
+  if (R->hashed) ganon_nh::key_state(key, key_len, &R->name_key);
+  return 0;
+}
+
 GANON_HOST_API int ganon_bam_reader_has_index(const ganon_bam_reader *R) { return R && R->has_index ? 1 : 0; }
 
 GANON_HOST_API int ganon_bam_reader_header(ganon_bam_reader *R, ganon_bam_view *v) {
@@ -1076,7 +1140,7 @@ GANON_HOST_API int ganon_bam_reader_contig(ganon_bam_reader *R, int32_t tid, gan
     bam->ref_names = R->header.ref_names;
     bam->ref_name_off = R->header.ref_name_off;
     bam->ref_len = R->header.ref_len;
-    if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs) != 0) {
+    if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs, R->hashed ? &R->name_key : nullptr) != 0) {
       delete bam;
       return -1;
     }
@@ -1136,7 +1200,7 @@ GANON_HOST_API int ganon_bam_reader_region(ganon_bam_reader *R, int32_t tid, int
       *out = bam;
       return 0;
     }
-    if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs) != 0) {
+    if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs, R->hashed ? &R->name_key : nullptr) != 0) {
       delete bam;
       return -1;
     }

@@ -402,6 +402,8 @@ def run_pairs_sharded(vcfs: Sequence[str], samples: Sequence[tuple], ref_file: s
     from .planner import get_windows
     from .stream import anonymize_genome_streaming
     rank, world = dist.get_rank(), dist.get_world_size()
+    from . import native
+    native.share_read_name_key(dist)   # --hash_read_names: rank 0's key for every pair on every rank
     fa = FastaRef(ref_file)
     out: List[dict] = []
     if len(samples) >= world:

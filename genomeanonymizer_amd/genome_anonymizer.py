@@ -2,7 +2,7 @@
 
   python -m genomeanonymizer_amd.genome_anonymizer -d DIR -s samples.tsv -r ref.fa \\
       [-m complete_germline] [-c CPUS] [--record_statistics] [--enhanced_multiprocessing] [-v N]
-      [--compress_output] [--masked_base_quality Q]
+      [--compress_output] [--masked_base_quality Q] [--hash_read_names]
 
 samples.tsv: tumor<TAB>normal<TAB>vcf per line, paths relative to DIR, '#' lines skipped.
 Outputs next to the inputs: re.sub('.bam|.sam|.cram', '.anonymized', path) + .1/.2.fastq
@@ -12,6 +12,14 @@ instead, BGZF members deflated on the GPU; GANON_COMPRESS_OUTPUT=1 is the same d
 --masked_base_quality Q (an extension, 0..93; GANON_MASKED_BASE_QUALITY=Q is the same default): every
 base a germline SNV mask wrote is printed with quality chr(33 + Q), so that a caller run on the
 anonymized FASTQ does not read the synthetic base with the confidence of the one sequenced there.
+--hash_read_names (an extension; GANON_HASH_READ_NAMES=1 is the same default): every read name is
+replaced, where its record is decoded, by hex(BLAKE2s(name, key=K, digest_size=16)), 32 hex characters
+— an Illumina name holds instrument, run, flowcell, lane, tile and x/y. Mates still pair (equal names
+hash equally); record order, which records are mates and the /1 and /2 suffixes stay as they are. K
+comes from GANON_READ_NAME_KEY (2 to 64 hex digits; there is no key flag: it would show in ps). Without
+it 32 random bytes are drawn once per invocation: the names are then unlinkable and the run cannot be
+repeated. A supplied key makes runs reproducible and must be kept as secret as the original names.
+The key is never logged or written; one key serves every pair of the invocation, tumor and normal.
 
 Multi-GPU: launch under ``torchrun --nproc-per-node N`` (or set WORLD_SIZE/RANK/LOCAL_RANK):
 contigs are sharded round-robin over the ranks; each rank decodes, masks and writes its own
@@ -58,6 +66,9 @@ def exec_parser(argv=None):
     parser.add_argument("--masked_base_quality", type=int, choices=range(0, 94), metavar="Q", default=None,
                         help="Phred quality 0..93 printed under every base a germline SNV mask wrote "
                              "(default: GANON_MASKED_BASE_QUALITY, else the qualities stay as they are)")
+    parser.add_argument("--hash_read_names", action=BooleanOptionalAction,
+                        help="Replace every read name by its keyed BLAKE2s-128 hash, 32 hex characters (default: "
+                             "GANON_HASH_READ_NAMES; key: GANON_READ_NAME_KEY as hex, else random per invocation)")
     parser.add_argument("-v", "--verbose", type=int, required=False, default=2, help="Verbosity of logging")
     parser.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     return parser.parse_args(argv)
@@ -95,6 +106,15 @@ def run_anonymizer(argv=None) -> None:
         os.environ["GANON_COMPRESS_OUTPUT"] = "1" if config.compress_output else "0"
     if config.masked_base_quality is not None:
         os.environ["GANON_MASKED_BASE_QUALITY"] = str(config.masked_base_quality)
+    if config.hash_read_names is not None:
+        os.environ["GANON_HASH_READ_NAMES"] = "1" if config.hash_read_names else "0"
+    from . import native
+    try:   # (a malformed key ends the run here, before any file is opened)
+        if os.environ.get("GANON_HASH_READ_NAMES", "0") == "1" and native.NAME_KEY_ENV in os.environ:
+            native.parse_name_key(os.environ[native.NAME_KEY_ENV])
+    except native.GanonError as e:
+        logging.error("%s", e)
+        sys.exit(1)
     vcfs, samples, outputs = read_samples(join_dir_file(config.directory, config.samples), config.directory)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -117,6 +137,7 @@ def run_anonymizer(argv=None) -> None:
             dist.init_process_group("nccl", device_id=torch.device("cuda", device))
         logging.info("rank %d of %d: process group backend %s", dist.get_rank(), dist.get_world_size(),
                      dist.get_backend())
+        native.share_read_name_key(dist)   # rank 0's key on every rank, before any rank opens a reader
         # one pair per GPU when there are enough pairs, else each pair's contigs over all GPUs
         tots = run_pairs_sharded(vcfs, samples, config.reference, anonymizer, outputs, bool(config.record_statistics),
                                  dist, threads=max(1, config.cpu))
@@ -125,6 +146,7 @@ def run_anonymizer(argv=None) -> None:
         release_side_groups(dist)
         dist.destroy_process_group()
     else:
+        native.share_read_name_key(draw=True)   # (in the environment: spawned pair workers inherit it)
         run_short_read_tumor_normal_anonymizer(vcfs, samples, config.reference, anonymizer, outputs,
                                                bool(config.record_statistics), config.cpu,
                                                bool(config.enhanced_multiprocessing))

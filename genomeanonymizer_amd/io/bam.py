@@ -60,13 +60,19 @@ def _view(ptr, n, dtype, owner: _Decoded):
 class ReadTable:
     """All records of one BAM file, in file order."""
 
-    def __init__(self, path: str, threads: int = 8, handle=None):
+    def __init__(self, path: str, threads: int = 8, handle=None, name_key: Optional[bytes] = None):
         """Decode the whole file, or take the records of an open ``ganon_bam`` handle (one
-        reference sequence from ``BamReader.contig``); the table owns the handle from here on."""
+        reference sequence from ``BamReader.contig``); the table owns the handle from here on.
+        ``name_key`` (--hash_read_names): every name is replaced, as it is decoded, by
+        hex(BLAKE2s(name, key, digest_size=16)) (``ganon_bam_open_keyed``); a handle's names are
+        whatever its reader decoded."""
         lib = native.host_lib()
         if handle is None:
             h = C.c_void_p()
-            rc = lib.ganon_bam_open(os.fsencode(path), int(threads), C.byref(h))
+            if name_key:
+                rc = lib.ganon_bam_open_keyed(os.fsencode(path), int(threads), bytes(name_key), len(name_key), C.byref(h))
+            else:
+                rc = lib.ganon_bam_open(os.fsencode(path), int(threads), C.byref(h))
             if rc != 0:
                 raise native.GanonError(f"cannot decode {path}: {lib.ganon_host_last_error().decode()}")
         else:
@@ -248,9 +254,12 @@ class BamReader:
     ganon_host.h): the bounded-memory counterpart of ``ReadTable(path)``. ``contig(tid)`` returns a
     ReadTable of that sequence's records only (file order, full reference list); the reader seeks
     through ``<bam>.bai`` when present, else streams forward. ``inflater``: a native.GpuInflater
-    that inflates the reader's BGZF block windows instead of its zlib threads."""
+    that inflates the reader's BGZF block windows instead of its zlib threads. ``name_key``
+    (--hash_read_names): every table carries hashed names (``ganon_bam_reader_set_name_key``), and an
+    inflater set on the reader hashes with the same key on the device (``GpuInflater.set_name_key``)."""
 
-    def __init__(self, path: str, threads: int = 8, window: int = 0, inflater=None):
+    def __init__(self, path: str, threads: int = 8, window: int = 0, inflater=None,
+                 name_key: Optional[bytes] = None):
         lib = native.host_lib()
         h = C.c_void_p()
         rc = lib.ganon_bam_reader_open(os.fsencode(path), int(threads), C.byref(h))
@@ -258,6 +267,11 @@ class BamReader:
             raise native.GanonError(f"cannot open {path}: {lib.ganon_host_last_error().decode()}")
         self._h = h
         self.path = path
+        self.name_key = bytes(name_key) if name_key else None
+        if self.name_key and lib.ganon_bam_reader_set_name_key(h, self.name_key, len(self.name_key)) != 0:
+            msg = lib.ganon_host_last_error().decode()
+            self.close()
+            raise native.GanonError(msg)
         if window:
             lib.ganon_bam_reader_set_window(h, int(window))
         self.inflater = None
@@ -274,6 +288,11 @@ class BamReader:
     def set_inflater(self, inflater) -> None:
         """Block windows inflate on the GPU from now on (a native.GpuInflater, kept alive here: the
         reader calls into its context)."""
+        if hasattr(inflater, "set_name_key"):
+            # (set or cleared on every attach: the inflaters are kept across runs, stream._INFLATERS)
+            inflater.set_name_key(self.name_key)
+        elif self.name_key:
+            raise native.GanonError("this inflater cannot hash read names (no set_name_key)")
         native.host_lib().ganon_bam_reader_set_inflater(self._h, inflater.fn, inflater.handle, inflater.min_blocks)
         self.inflater = inflater
         if isinstance(inflater, native.GpuInflater) and os.environ.get("GANON_PINNED_SCAN", "1") != "0":

@@ -13,7 +13,7 @@ import os
 import threading
 import weakref
 import time
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -218,6 +218,7 @@ def hip_lib():
     lib.ganon_bam_dcols_get.argtypes = [_p, C.POINTER(BamCols), _i64p]
     lib.ganon_bam_dcols_download.argtypes = [_p, _p, C.POINTER(BamCols)]
     lib.ganon_bam_dcols_free.argtypes = [_p, _p]
+    lib.ganon_ctx_set_name_key.argtypes = [_p, C.c_char_p, C.c_int32]
     lib.ganon_deflate_bound.argtypes = [C.c_int64, C.c_int32]
     lib.ganon_deflate_bound.restype = C.c_int64
     lib.ganon_deflate_bgzf.argtypes = [_p, _u8p, C.c_int64, C.c_int32, _u8p, C.c_int64, _i64p, _i32p]
@@ -257,6 +258,7 @@ EXPORTED_HIP_SYMBOLS = (
     "ganon_indel_upload", "ganon_indel_run", "ganon_indel_download", "ganon_indel_info", "ganon_indel_free",
     "ganon_inflate", "ganon_inflate_hostcb", "ganon_inflate_device_output",
     "ganon_bam_columns", "ganon_bam_dcols_get", "ganon_bam_dcols_download", "ganon_bam_dcols_free",
+    "ganon_ctx_set_name_key",
     "ganon_pinned_alloc", "ganon_pinned_free", "ganon_pinned_stats", "ganon_region_decode",
     "ganon_deflate_bound", "ganon_deflate_bgzf",
 )
@@ -272,6 +274,7 @@ EXPORTED_HOST_SYMBOLS = (
     "ganon_objects_run", "ganon_objects_take", "ganon_objects_settle", "ganon_objects_last_error",
     "ganon_objects_take_all", "ganon_aux_sa_count", "ganon_fastq_edit", "ganon_gather_ranges", "ganon_gather_ranges2", "ganon_host_phase_times",
     "ganon_bam_reader_set_inflater", "ganon_bam_reader_set_buffer_alloc", "ganon_bam_reader_set_region_decoder",
+    "ganon_bam_open_keyed", "ganon_names_hash", "ganon_bam_reader_set_name_key",
 )
 
 
@@ -348,6 +351,7 @@ class GpuInflater:
         self.min_blocks = int(min_blocks)
         self.fn = C.cast(lib.ganon_inflate_hostcb, _p)   # the reader's callback, user = the context
         self.region_fn = C.cast(lib.ganon_region_decode, _p)   # the reader's region decoder, same user
+        self.name_key: Optional[bytes] = None
 
     @property
     def handle(self):
@@ -356,11 +360,25 @@ class GpuInflater:
     def set_profiling(self, on: bool) -> None:
         self._lib.ganon_ctx_set_profiling(self._h, 1 if on else 0)
 
+    def set_name_key(self, key: Optional[bytes]) -> None:
+        """--hash_read_names: the context's BAM decoder (``bam_columns``, the region decoder) returns
+        hashed read names from now on (``ganon_ctx_set_name_key``); None or empty turns it off."""
+        key = bytes(key or b"")
+        if self._lib.ganon_ctx_set_name_key(self._h, key, len(key)) != 0:
+            raise GanonError(self._lib.ganon_last_error(self._h).decode(errors="replace"))
+        self.name_key = key or None
+
     def kernel_ms(self) -> float:
         """k_inflate's time in the last profiled inflate (HIP events on the context's stream)."""
         arr = (KernelTime * 4)()
         n = self._lib.ganon_last_kernel_times(self._h, arr, 4)
         return sum(float(arr[i].ms) for i in range(min(n, 4)) if arr[i].name == b"k_inflate")
+
+    def kernel_times(self) -> List[Tuple[str, float]]:
+        """(kernel, ms) of the context's last profiled call, in launch order (``ganon_last_kernel_times``)."""
+        arr = (KernelTime * 64)()
+        n = self._lib.ganon_last_kernel_times(self._h, arr, 64)
+        return [(arr[i].name.decode(), float(arr[i].ms)) for i in range(min(n, 64))]
 
     def inflate(self, comp: np.ndarray, in_off: np.ndarray, in_len: np.ndarray, out_len: np.ndarray) -> np.ndarray:
         """Inflate raw DEFLATE payloads comp[in_off[i]:+in_len[i]] (each to out_len[i] bytes),
@@ -443,6 +461,72 @@ def compress_output_default() -> bool:
     """``GANON_COMPRESS_OUTPUT=1``: BGZF-compressed FASTQ output (``--compress_output``) for library
     callers and for spawned pair workers and ranks."""
     return os.environ.get("GANON_COMPRESS_OUTPUT", "0") == "1"
+
+
+NAME_KEY_ENV = "GANON_READ_NAME_KEY"
+
+
+def parse_name_key(text: str) -> bytes:
+    """The key of ``GANON_READ_NAME_KEY``: 1 to 32 bytes as hex. The value is never quoted in the error."""
+    t = text.strip()
+    if not t or len(t) % 2 or len(t) > 64 or any(c not in "0123456789abcdefABCDEF" for c in t):
+        raise GanonError(f"{NAME_KEY_ENV}: 2 to 64 hex digits (a key of 1 to 32 bytes), an even number of them")
+    return bytes.fromhex(t)
+
+
+def read_name_key_default() -> Optional[bytes]:
+    """``GANON_HASH_READ_NAMES=1`` (``--hash_read_names``): the key every BAM decode of this process
+    hashes the read names with, from ``GANON_READ_NAME_KEY`` (hex) — for library callers and for spawned
+    pair workers and ranks, which inherit both variables. None when the option is off. The option
+    without a key is an error here: only the command line draws a random one (and exports it), since
+    separate decodes with separate random keys would no longer pair mates."""
+    if os.environ.get("GANON_HASH_READ_NAMES", "0") != "1":
+        return None
+    v = os.environ.get(NAME_KEY_ENV)
+    if v is None:
+        raise GanonError(f"GANON_HASH_READ_NAMES=1 needs a key in {NAME_KEY_ENV} (hex, 1 to 32 bytes)")
+    return parse_name_key(v)
+
+
+def share_read_name_key(dist=None, draw: bool = False) -> Optional[bytes]:
+    """The run's key, agreed before any reader opens (None: the option is off). With ``dist`` (an
+    initialised torch.distributed) rank 0's key — the environment's, else 32 random bytes — is
+    broadcast, and every rank keeps it in its environment: mates decoded by different ranks pair only
+    under one key. ``draw``: a process without ranks draws a random key too (the command line, before it
+    spawns pair workers). The key is never logged."""
+    if os.environ.get("GANON_HASH_READ_NAMES", "0") != "1":
+        return None
+    if dist is not None:
+        box = [None]
+        if dist.get_rank() == 0:
+            v = os.environ.get(NAME_KEY_ENV)
+            try:
+                box[0] = parse_name_key(v) if v is not None else os.urandom(32)
+            except GanonError as e:   # (every rank raises it: none waits in the broadcast)
+                box[0] = str(e)
+        dist.broadcast_object_list(box, src=0)
+        if isinstance(box[0], str):
+            raise GanonError(box[0])
+        os.environ[NAME_KEY_ENV] = box[0].hex()
+    elif draw and NAME_KEY_ENV not in os.environ:
+        os.environ[NAME_KEY_ENV] = os.urandom(32).hex()
+    return read_name_key_default()
+
+
+def names_hash(names: Sequence[bytes], key: bytes, threads: int = 1) -> List[bytes]:
+    """``ganon_names_hash``: hex(BLAKE2s(name, key, digest_size=16)) of each name, by the decoder's core."""
+    n = len(names)
+    blob = np.frombuffer(b"".join(names), np.uint8)
+    ln = np.array([len(x) for x in names], np.int32)
+    off = np.zeros(n, np.int64)
+    if n > 1:
+        np.cumsum(ln[:-1], out=off[1:])
+    out = np.zeros(33 * n, np.uint8)
+    if host_lib().ganon_names_hash(blob.ctypes.data if len(blob) else None, _ptr(off, _i64p), _ptr(ln, _i32p), n,
+                                   bytes(key), len(key), int(threads), out.ctypes.data) != 0:
+        raise GanonError(host_lib().ganon_host_last_error().decode())
+    raw = out.tobytes()
+    return [raw[33 * i:33 * i + 32] for i in range(n)]
 
 
 def masked_base_quality_default() -> Optional[int]:
@@ -1672,6 +1756,9 @@ def host_lib():
         raise GanonError(f"{HOST_LIB_PATH} is missing: run __graft_entry__.build()")
     lib = C.CDLL(HOST_LIB_PATH)
     lib.ganon_bam_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(_p)]
+    lib.ganon_bam_open_keyed.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int32, C.POINTER(_p)]
+    lib.ganon_names_hash.argtypes = [C.c_void_p, _i64p, _i32p, C.c_int64, C.c_char_p, C.c_int32, C.c_int, C.c_void_p]
+    lib.ganon_bam_reader_set_name_key.argtypes = [_p, C.c_char_p, C.c_int32]
     lib.ganon_bam_view_get.argtypes = [_p, C.POINTER(BamView)]
     lib.ganon_bam_close.argtypes = [_p]
     lib.ganon_bam_reader_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(_p)]

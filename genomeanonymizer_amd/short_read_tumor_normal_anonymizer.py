@@ -67,8 +67,9 @@ def anonymize_genome(windows_in_sample: List[Window], tumor_bam_file: str, norma
                  timing)
         return timing
     t0 = time.time()
-    tumor = ReadTable(tumor_bam_file, threads=available_threads)
-    normal = ReadTable(normal_bam_file, threads=available_threads)
+    name_key = native.read_name_key_default()   # --hash_read_names (None: off)
+    tumor = ReadTable(tumor_bam_file, threads=available_threads, name_key=name_key)
+    normal = ReadTable(normal_bam_file, threads=available_threads, name_key=name_key)
     if has_split_alignments(tumor) or has_split_alignments(normal):
         log.info("secondary / supplementary alignments or SA tags: the sample streams contig by contig")
         del tumor, normal   # (the streamed path decodes job by job: do not hold the whole sample too)

@@ -1197,6 +1197,8 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
     paths = [f"{tumor_out}.1.fastq", f"{tumor_out}.2.fastq", f"{normal_out}.1.fastq", f"{normal_out}.2.fastq"]
     single_paths = (f"{tumor_out}.single_end.fastq", f"{normal_out}.single_end.fastq")
     compress = native.compress_output_default() if compress_output is None else bool(compress_output)
+    # --hash_read_names: one key for every reader of the run, rank 0's on every rank (None: off)
+    name_key = native.share_read_name_key(dist)
     deflater = None
     spools: List[str] = []
     segs: List[Tuple[int, int, int, int]] = []   # (job, file, spool offset, compressed length) of this rank's jobs
@@ -1228,7 +1230,8 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
             if os.path.exists(p):
                 os.remove(p)
         raise
-    readers = (BamReader(tumor_bam, threads, window_bytes), BamReader(normal_bam, threads, window_bytes))
+    readers = (BamReader(tumor_bam, threads, window_bytes, name_key=name_key),
+               BamReader(normal_bam, threads, window_bytes, name_key=name_key))
     # jobs: contigs, or runs of sections of about GANON_JOB_BP bases (default 4 Mb; 0 = whole
     # contigs) when both BAMs are indexed
     # (unset: 4 Mb, or smaller so that every rank gets about GANON_JOBS_PER_RANK jobs (default 3, at
@@ -1382,7 +1385,8 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
             job.forced = sorted(set(force) | set(job.forced))
             return job
         if not redo_readers:
-            redo_readers.extend(BamReader(p, threads, window_bytes) for p in (tumor_bam, normal_bam))
+            redo_readers.extend(BamReader(p, threads, window_bytes, name_key=name_key)
+                                for p in (tumor_bam, normal_bam))
         prep = JobPrep(job.spec, redo_readers, fasta, windows, secondaries=secondaries, force=force)
         done = Future()
         done.set_result(prep)
@@ -1475,7 +1479,8 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
                         timing["spec_replans"] = timing.get("spec_replans", 0) + 1
                         job.release_device()
                         if not redo_readers:
-                            redo_readers.extend(BamReader(p, threads, window_bytes) for p in (tumor_bam, normal_bam))
+                            redo_readers.extend(BamReader(p, threads, window_bytes, name_key=name_key)
+                                                for p in (tumor_bam, normal_bam))
                         prep = JobPrep(job.spec, redo_readers, fasta, windows, secondaries=secondaries, force=full)
                         done = Future()
                         done.set_result(prep)

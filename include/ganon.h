@@ -441,6 +441,15 @@ GANON_API int ganon_bam_dcols_get(const ganon_bam_dcols *c, ganon_bam_cols *devi
 GANON_API int ganon_bam_dcols_download(ganon_ctx *ctx, const ganon_bam_dcols *c, const ganon_bam_cols *host);
 /* (with the context that made it: its device blocks return to that context's cache) */
 GANON_API int ganon_bam_dcols_free(ganon_ctx *ctx, ganon_bam_dcols *c);
+/* --hash_read_names (additive; the ABI version stays 5). ganon_ctx_set_name_key(ctx, key, 1..32): from
+ * now on ganon_bam_columns and ganon_region_decode on this context return every record's name
+ * replaced by hex(BLAKE2s(name, key, digest_size = 16)), 32 lowercase hex characters (RFC 7693 keyed
+ * mode; include/ganon_host.h ganon_bam_open_keyed gives the same bytes on the host): name_len = 32,
+ * name_off[i] = 33 i, one NUL per name, every other column and blob unchanged. The names are hashed
+ * on the device by k_bam_name_hash (listed in ganon_last_kernel_times when profiling); no name goes
+ * to the host to be hashed. key_len 0 clears the key: no kernel is added and the decoder's kernels
+ * are those of a context that never had one. The key is kept in the context only. */
+GANON_API int ganon_ctx_set_name_key(ganon_ctx *ctx, const uint8_t *key, int32_t key_len);
 
 /* A region read's window decoded on the device: the reader's region decoder (ganon_region_fn of
  * include/ganon_host.h, user = a ganon_ctx; libganon_host.so's ganon_bam_reader_region, the

@@ -55,6 +55,20 @@ typedef struct ganon_bam_view {
 
 /* Decode the whole file (BGZF inflate on `threads` threads). Returns 0 or <0. */
 GANON_HOST_API int ganon_bam_open(const char *path, int threads, ganon_bam **out);
+/* --hash_read_names (additive). ganon_bam_open with every record's name replaced, where it is decoded,
+ * by hex(BLAKE2s(name, key, digest_size = 16)) — RFC 7693 keyed mode, 32 lowercase hex characters,
+ * what Python's hashlib.blake2s(name, key=key, digest_size=16).hexdigest() returns. The hashed bytes are
+ * those the unkeyed decoder reports as the name (names[name_off, + name_len), the empty name
+ * included). name_len is 32 for every record and the blob keeps one NUL per name (name_off[i] = 33 i);
+ * every other column and blob is what ganon_bam_open returns. key_len 1..32. No key is kept in
+ * process-global state: it lives in the table's decode (here) or in the reader
+ * (ganon_bam_reader_set_name_key). */
+GANON_HOST_API int ganon_bam_open_keyed(const char *path, int threads, const uint8_t *key, int32_t key_len,
+                                        ganon_bam **out);
+/* The same hash over n names, names[off[i], + len[i]) (len 0..255), on `threads` threads: out[33 i, + 33) =
+ * the 32 characters and a NUL. For tests and tools. */
+GANON_HOST_API int ganon_names_hash(const char *names, const int64_t *off, const int32_t *len, int64_t n,
+                                    const uint8_t *key, int32_t key_len, int threads, char *out);
 GANON_HOST_API int ganon_bam_view_get(ganon_bam *bam, ganon_bam_view *view);
 GANON_HOST_API const char *ganon_bam_error(ganon_bam *bam);
 GANON_HOST_API void ganon_bam_close(ganon_bam *bam);
@@ -108,6 +122,12 @@ typedef int (*ganon_region_fn)(void *user, const uint8_t *comp, int64_t comp_len
                                int64_t beg, int64_t end, int at_eof, ganon_bam_view *cols, void **block);
 GANON_HOST_API int ganon_bam_reader_set_region_decoder(ganon_bam_reader *reader, ganon_region_fn fn, void *user,
                                                        int64_t min_blocks, ganon_buf_free_fn release);
+/* --hash_read_names: the tables of ganon_bam_reader_contig and ganon_bam_reader_region carry hashed
+ * names from now on (ganon_bam_open_keyed), hashed on the reader's threads inside the column pass —
+ * the host path of a region read too, where the region decoder declines a window or the region runs
+ * past it. A region decoder must hash with the same key (ganon_ctx_set_name_key on its context).
+ * key_len 0 turns it off. */
+GANON_HOST_API int ganon_bam_reader_set_name_key(ganon_bam_reader *reader, const uint8_t *key, int32_t key_len);
 GANON_HOST_API int ganon_bam_reader_header(ganon_bam_reader *reader, ganon_bam_view *view);
 GANON_HOST_API int ganon_bam_reader_contig(ganon_bam_reader *reader, int32_t tid, ganon_bam **out);
 /* The records of tid overlapping [beg, end) (0-based; htslib's region semantics: pos < end and

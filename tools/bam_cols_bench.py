@@ -8,6 +8,10 @@ libganon_host.so's ganon_bam_open on the same records written as stored (level-0
 that its inflate is a copy and the time is mostly the record walk's (one thread and --threads
 threads; the file read included). Every device column must equal the host decoder's. Prints one
 JSON line (bench.py's `bam_decode` side line runs this as a child).
+
+--hash_names: the same with a read-name key on both sides (--hash_read_names: GANON_READ_NAME_KEY as
+hex, else a fixed benchmark key): k_bam_name_hash joins the kernel list, the names block is 33 bytes a
+record, and the host decoder hashes inside its column pass.
 """
 import argparse
 import json
@@ -27,7 +31,10 @@ BLOBS = ("names_blob", "cigar", "seq", "qual", "aux")
 HBM_PEAK_GBPS = 8000.0
 
 
-def measure(mb: int = 256, threads: int = 16, reps: int = 3) -> dict:
+BENCH_KEY = bytes(range(32))
+
+
+def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = None) -> dict:
     import gzip
     from genomeanonymizer_amd import native
     from genomeanonymizer_amd.io.bam import ReadTable
@@ -44,6 +51,7 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3) -> dict:
         g = native.GpuInflater(0, min_blocks=1)
         lib = native.hip_lib()
         g.set_profiling(True)
+        g.set_name_key(name_key)
         runs = []
         cols, _ = native.bam_columns_device(g.handle, stream, p, len(stream), on_host=True)   # (warm: blocks cached)
         for _ in range(reps):
@@ -66,7 +74,7 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3) -> dict:
         t = None
         for th in (1, threads):
             t0 = time.perf_counter()
-            t = ReadTable(path, threads=th)
+            t = ReadTable(path, threads=th, name_key=name_key)
             host[th] = time.perf_counter() - t0
         equal = len(cols["pos"]) == t.n and all(np.array_equal(cols[f], getattr(t, f)) for f in COLS + BLOBS)
         out_bytes = sum(cols[f].nbytes for f in COLS + BLOBS) + cols["rec_off"].nbytes
@@ -82,7 +90,7 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3) -> dict:
             "device_call_wall_s": round(best[2], 3), "guess_fixes": best[3],
             "host_decoder_s": {str(k): round(v, 3) for k, v in host.items()},
             "host_records_per_s": {str(k): round(nr / v, 1) for k, v in host.items()},
-            "columns_equal_host_decoder": bool(equal),
+            "columns_equal_host_decoder": bool(equal), "hashed_names": name_key is not None,
             "workload": f"configs[0] tumor BAM records tiled x{tiles} ({nr} records, 150 bp); device: the stream "
                         f"resident in HBM, kernels only (HIP events on the context's stream); call wall adds the H2D "
                         f"copy, the scans' host reads and the D2H of the columns; host: ganon_bam_open of the same "
@@ -97,8 +105,15 @@ def main() -> None:
     ap.add_argument("--mb", type=int, default=256)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--hash_names", action="store_true",
+                    help="decode with a read-name key (GANON_READ_NAME_KEY as hex, else a fixed benchmark key)")
     args = ap.parse_args()
-    print(json.dumps(measure(args.mb, args.threads, args.reps)))
+    key = None
+    if args.hash_names:
+        from genomeanonymizer_amd import native
+        v = os.environ.get(native.NAME_KEY_ENV)
+        key = native.parse_name_key(v) if v is not None else BENCH_KEY
+    print(json.dumps(measure(args.mb, args.threads, args.reps, key)))
 
 
 if __name__ == "__main__":

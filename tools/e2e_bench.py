@@ -21,6 +21,8 @@ Prints one JSON line with per-stage seconds, reads/s, bases/s and the process's 
                              # line with "compress_output": true, for the price of the flag
     GANON_MASKED_BASE_QUALITY=Q  # --masked_base_quality: masked bases printed with quality Q: the
                              # same line with "masked_base_quality": Q
+    GANON_HASH_READ_NAMES=1 GANON_READ_NAME_KEY=HEX  # --hash_read_names: read names hashed at decode (DESIGN
+                             # §4h): the same line with "hash_read_names": true
     E2E_DISK_PROBE=1 ...     # also time 2 GiB of pwrite into OUTDIR (4 files at once, as the product
                              # writes; page cache, then with fsync): the box's write bandwidth
 """
@@ -214,6 +216,7 @@ def main():
                      "cpu_us_per_read": round(best["cpu_s"] / max(1, best["reads"]) * 1e6, 3),
                      "compress_output": bool(gz),
                      "masked_base_quality": _native.masked_base_quality_default(),
+                     "hash_read_names": _native.read_name_key_default() is not None,
                      "cpus_available": len(os.sched_getaffinity(0)),
                      "output_bytes": sum(os.path.getsize(os.path.join(out, f"{x}_{mode}{s}{gz}"))
                                          for x in ("tumor", "normal") for s in (".1.fastq", ".2.fastq"))}

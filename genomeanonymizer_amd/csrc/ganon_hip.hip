@@ -332,8 +332,9 @@ struct GrpBatch {
   const int32_t *keep_pos, *span_start, *span_len;
 };
 
-// OBS: observations held in LDS before a list overflows into the group's global region (512; 1024
-// for deep-coverage batches, ganon_batch_run picks it); the in-partition mask list has the same size.
+// OBS: observations held in LDS before a list overflows into the group's global region (512, which
+// ganon_batch_run always picks on its own; 1024 only when GANON_PARAM_GROUP_OBS asks for it); the
+// in-partition mask list has the same size.
 template <int OBS>
 struct GrpSharedT {
   static constexpr int kObs = OBS;
@@ -2420,6 +2421,33 @@ void new_step(ganon_ctx *ctx) {
   }
   ctx->recs.clear();
 }
+
+// The compiled k_group instantiations, one table for the three families (FLAT fused, LONG, record
+// pass): unroll 1, 2, 4, 8 with the 512-entry observation list, 1 and 2 with the 1024-entry one.
+// Null: the pair is not compiled (ganon_batch_run refuses it; no other pair runs in its place).
+using GroupKernel = void (*)(const GrpBatch, const int4 *, const int4 *, uint8_t *, const GrpAux *, int, int,
+                             const unsigned long long *, const int32_t *);
+template <bool FLAT, bool LONG>
+GroupKernel group_kernel_of(int u, int obs) {
+  if (obs == 512) {
+    switch (u) {
+      case 1: return k_group<1, true, 512, FLAT, LONG>;
+      case 2: return k_group<2, true, 512, FLAT, LONG>;
+      case 4: return k_group<4, true, 512, FLAT, LONG>;
+      case 8: return k_group<8, true, 512, FLAT, LONG>;
+    }
+  } else if (obs == 1024) {
+    switch (u) {
+      case 1: return k_group<1, true, 1024, FLAT, LONG>;
+      case 2: return k_group<2, true, 1024, FLAT, LONG>;
+    }
+  }
+  return nullptr;
+}
+GroupKernel group_kernel(bool fused, bool long_mode, int u, int obs) {
+  return fused ? group_kernel_of<true, false>(u, obs)
+               : long_mode ? group_kernel_of<false, true>(u, obs) : group_kernel_of<false, false>(u, obs);
+}
 }  // namespace
 
 GANON_API int ganon_batch_replan(ganon_ctx *ctx, ganon_dbatch *db) {
@@ -2440,6 +2468,17 @@ GANON_API int ganon_batch_replan(ganon_ctx *ctx, ganon_dbatch *db) {
 
 GANON_API int ganon_batch_run(ganon_ctx *ctx, ganon_dbatch *db) {
   if (!ctx || !db) return fail(ctx, GANON_E_ARG, "null argument");
+  // 16-base chunks per thread: long reads (short segments between indels) waste less with one
+  // (profiles/r02/sweep_c5.jsonl); short reads run best with two (sweep_c3.jsonl, DESIGN 5)
+  const int u = ctx->group_unroll ? ctx->group_unroll : db->long_mode ? 1 : 2;
+  // 512 unless forced: the 1024-entry list (4 workgroups per CU instead of 6) measured slower on
+  // c3 too (3.19 vs 2.84 ms, profiles/r02/sweep_c3_obs.jsonl) — occupancy outweighs the region path
+  const int obs = ctx->group_obs ? ctx->group_obs : 512;
+  // (before anything is launched: a pair without a compiled kernel never runs another pair's)
+  if (!group_kernel(db->fused, db->long_mode, u, obs))
+    return fail(ctx, GANON_E_ARG,
+                "no group kernel is compiled for GANON_PARAM_GROUP_UNROLL %d with GANON_PARAM_GROUP_OBS %d "
+                "(the 1024-entry list takes unroll 1 or 2)", u, obs);
   HIP_OR_FAIL(hipSetDevice(ctx->device));
   if (!ctx->step_open) new_step(ctx);
   ctx->step_open = false;
@@ -2447,9 +2486,6 @@ GANON_API int ganon_batch_run(ganon_ctx *ctx, ganon_dbatch *db) {
   DevBatch B = db->B;
   if (!ctx->ref2) B.ref2 = nullptr;   // group kernels then read the nt16 reference only
   int rc;
-  // 16-base chunks per thread: long reads (short segments between indels) waste less with one
-  // (profiles/r02/sweep_c5.jsonl); short reads run best with two (sweep_c3.jsonl, DESIGN 5)
-  const int u = ctx->group_unroll ? ctx->group_unroll : db->long_mode ? 1 : 2;
   // 1. derived layer from the raw SoA
   if ((rc = ganon_prep::run(ctx, db))) return rc;
   if (ctx->indel_fork < 0) {
@@ -2469,20 +2505,7 @@ GANON_API int ganon_batch_run(ganon_ctx *ctx, ganon_dbatch *db) {
   // 2. masking: the fused group kernel writes every byte of out (its pieces tile [0, seq_bytes))
   if (db->n_groups) {
     KernelScope ks(ctx, "k_group_fused");
-    // 512 unless forced: the 1024-entry list (4 workgroups per CU instead of 6) measured slower on
-    // c3 too (3.19 vs 2.84 ms, profiles/r02/sweep_c3_obs.jsonl) — occupancy outweighs the region path
-    const int obs = ctx->group_obs ? ctx->group_obs : 512;
-    auto kern = db->fused
-                    ? (obs == 1024 ? (u == 1 ? k_group<1, true, 1024, true> : k_group<2, true, 1024, true>)
-                                   : u == 2 ? k_group<2, true, 512, true> : u == 4 ? k_group<4, true, 512, true>
-                                   : u == 8 ? k_group<8, true, 512, true> : k_group<1, true, 512, true>)
-                : db->long_mode
-                    ? (obs == 1024 ? (u == 1 ? k_group<1, true, 1024, false, true> : k_group<2, true, 1024, false, true>)
-                                   : u == 2 ? k_group<2, true, 512, false, true> : u == 4 ? k_group<4, true, 512, false, true>
-                                   : u == 8 ? k_group<8, true, 512, false, true> : k_group<1, true, 512, false, true>)
-                    : (obs == 1024 ? (u == 1 ? k_group<1, true, 1024, false> : k_group<2, true, 1024, false>)
-                                   : u == 2 ? k_group<2, true, 512, false> : u == 4 ? k_group<4, true, 512, false>
-                                   : u == 8 ? k_group<8, true, 512, false> : k_group<1, true, 512, false>);
+    const GroupKernel kern = group_kernel(db->fused, db->long_mode, u, obs);
     const GrpBatch GB{B.seq, B.ref, B.keep_code, B.ref2, B.keep_pos, B.span_start, B.span_len};
     kern<<<db->n_groups, kGrpThreads, 0, st>>>(GB, static_cast<const int4 *>(db->b_groups.p),
                                                static_cast<const int4 *>(db->b_seg4.p), db->out, db->aux,

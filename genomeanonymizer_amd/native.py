@@ -756,7 +756,8 @@ class HipMasker:
         self._check(self._lib.ganon_ctx_set_variant(self._h, int(variant)), "set_variant")
 
     def set_param(self, param: int, value: int) -> None:
-        """include/ganon.h GANON_PARAM_* tuning knob (never changes results)."""
+        """include/ganon.h GANON_PARAM_* tuning knob (never changes results). PARAM_GROUP_UNROLL 4 or 8
+        with PARAM_GROUP_OBS 1024 has no compiled kernel: ``DeviceBatch.run`` then raises GanonError."""
         self._check(self._lib.ganon_ctx_set_param(self._h, int(param), int(value)), "set_param")
 
     def set_profiling(self, on: bool) -> None:

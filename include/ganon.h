@@ -120,7 +120,7 @@ GANON_API int ganon_ctx_set_variant(ganon_ctx *ctx, int variant);
  * the classification, bit 1 the chunk scan, bit 2 the partition copy of the group kernels, bit 3
  * the per-scope count stores.
  * Keep it 0 in production. GANON_PARAM_GROUP_TARGET: segments per scope group (read at
- * upload, in cost units: segments plus 3 per scope; 0 (default) = 1408 in long-read prep mode, else 704). GANON_PARAM_NT_COPY: non-temporal stores for the fused partition copy
+ * upload, in cost units: segments plus 3 per scope; 0 (default) = 2816 in long-read prep mode, else 704). GANON_PARAM_NT_COPY: non-temporal stores for the fused partition copy
  * (default 1). GANON_PARAM_REF2: group kernels read a 2-bit copy of the reference for segments
  * whose reference range is all ACGT (1, default) or the nt16 reference only (0).
  * GANON_PARAM_FASTQ_KD: FASTQ formatter kernel: 0 (default) = 16-byte units with per-span window
@@ -165,7 +165,9 @@ enum { GANON_PARAM_GROUP_UNROLL = 1, GANON_PARAM_GROUP_SKIP = 2, GANON_PARAM_GRO
 /* GANON_PARAM_PREP_UNROLL: incidences each thread of the one-segment prep emit takes per trip (1, 2,
  * 4; 0 = default). */
 /* GANON_PARAM_GROUP_OBS: observations a group keeps in LDS before its list overflows into the global
- * region: 512 (0, default) or 1024 (fewer resident workgroups; slower on every measured config). */
+ * region: 512 (0, default) or 1024 (fewer resident workgroups; slower on every measured config). The
+ * group kernels are compiled for GANON_PARAM_GROUP_UNROLL 1, 2, 4 and 8 with 512 and for 1 and 2 with
+ * 1024: ganon_batch_run fails with GANON_E_ARG, before it launches anything, for 4 or 8 with 1024. */
 GANON_API int ganon_ctx_set_param(ganon_ctx *ctx, int param, int value);
 /* When on, ganon_batch_run records a HIP event pair around each kernel it launches. */
 GANON_API int ganon_ctx_set_profiling(ganon_ctx *ctx, int enabled);

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Sweep the group kernel's tuning knobs (GANON_PARAM_GROUP_UNROLL, GANON_PARAM_GROUP_TARGET) on one
 bench configuration: the batch is generated and uploaded once, each setting is timed over K steps of
-``ganon_batch_run`` (device prep + masking), with per-kernel HIP-event times; totals must agree.
+``ganon_batch_run`` (device prep + masking), with per-kernel HIP-event times. ``same``: the setting's
+downloaded per-scope calls and bases, a checksum of its masked bases and its totals all equal the
+first setting's. Pairs without a compiled kernel (unroll 4 or 8 with the 1024-entry list) are skipped.
 
     python tools/sweep_group.py c3 [K]     # prints one JSON line per setting, then the best
 """
@@ -14,8 +16,15 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
+def compiled(unroll: int, obs: int) -> bool:
+    """Whether the library has a group kernel for the pair (include/ganon.h GANON_PARAM_GROUP_OBS): the
+    1024-entry observation list only with unroll 1 or 2 (0: auto, which is one of them)."""
+    return obs != 1024 or unroll in (0, 1, 2)
+
+
 def main():
     import argparse
+    import zlib
     import numpy as np
     import torch
     import bench
@@ -40,8 +49,12 @@ def main():
     pu_list = (1, 2, 4) if mode == "prep" else (0,)
     if mode == "prep":
         obs_list = pu_list
-    ref_tot, best, db, cur_t = None, None, None, None
+    ref_res, best, db, cur_t = None, None, None, None
     for (u, t), obs in [(x, o) for x in settings for o in obs_list]:
+        if not compiled(u, obs if mode != "prep" else 0):
+            # (ganon_batch_run refuses the pair: there is nothing to time under that label)
+            print(json.dumps({"config": cfg, "unroll": u, "target": t, "obs": obs, "skipped": "not compiled"}), flush=True)
+            continue
         if mode == "prep":
             m.set_param(native.PARAM_PREP_UNROLL, obs)
         else:
@@ -69,10 +82,17 @@ def main():
             for name, n, k_ms in db.kernel_times():
                 kt[name] = kt.get(name, 0.0) + k_ms / 5
         m.set_profiling(False)
-        tot = db.totals()[:2].tolist()
-        ref_tot = ref_tot or tot
+        # the whole result against the first setting's: the per-scope calls and bases, a checksum of
+        # the masked bases, the totals
+        out, calls, bases, totals = db.download()
+        tot = totals[:2].tolist()
+        res = (calls, bases, zlib.crc32(out), tot)
+        ref_res = ref_res or res
+        same = (np.array_equal(calls, ref_res[0]) and np.array_equal(bases, ref_res[1]) and res[2] == ref_res[2] and
+                tot == ref_res[3])
+        del out
         line = {"config": cfg, "unroll": u, "target": t, "obs": obs, "ms_per_step": round(ms, 4),
-                "kernels_ms": {k: round(v, 4) for k, v in kt.items()}, "totals": tot, "same": tot == ref_tot}
+                "kernels_ms": {k: round(v, 4) for k, v in kt.items()}, "totals": tot, "out_crc32": res[2], "same": same}
         print(json.dumps(line), flush=True)
         if best is None or ms < best[0]:
             best = (ms, u, t)

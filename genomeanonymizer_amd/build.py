@@ -43,8 +43,8 @@ def _run(cmd) -> None:
         raise RuntimeError(f"build failed: {' '.join(cmd)}")
 
 
-HIP_SOURCES = ("ganon_hip.hip", "ganon_prep.hip", "ganon_fastq.hip", "ganon_indel.hip", "ganon_inflate.hip",
-               "ganon_bam.hip", "ganon_deflate.hip")
+HIP_SOURCES = ("ganon_hip.hip", "ganon_group.hip", "ganon_huge.hip", "ganon_prep.hip", "ganon_fastq.hip",
+               "ganon_indel.hip", "ganon_inflate.hip", "ganon_bam.hip", "ganon_deflate.hip")
 
 
 def build_hip(force: bool = False) -> str:
@@ -112,8 +112,8 @@ def build_oracle(force: bool = False) -> str:
 # bench.py cites a summary only while the digest still matches: PMC bytes of older kernels are not
 # evidence for these)
 DIGEST_SOURCES = {
-    "mask": ("csrc/ganon_hip.hip", "csrc/ganon_prep.hip", "csrc/ganon_indel.hip", "csrc/ganon_ctx.h",
-             "csrc/ganon_batch.h", "../include/ganon.h"),
+    "mask": ("csrc/ganon_hip.hip", "csrc/ganon_group.hip", "csrc/ganon_huge.hip", "csrc/ganon_prep.hip",
+             "csrc/ganon_indel.hip", "csrc/ganon_ctx.h", "csrc/ganon_batch.h", "../include/ganon.h"),
     "fastq": ("csrc/ganon_fastq.hip", "csrc/ganon_ctx.h", "csrc/ganon_batch.h", "../include/ganon.h"),
 }
 

@@ -1,6 +1,6 @@
 // ganon_batch.h — internal to libganon_hip.so: the device batch (ganon_dbatch), the resident
 // reference (ganon_ref), the layouts the device prep kernels (ganon_prep.hip) write and the
-// masking kernels (ganon_hip.hip) read. Not part of the C ABI (include/ganon.h is).
+// masking kernels (ganon_group.hip, ganon_huge.hip; k_finish in ganon_hip.hip) read. Not part of the C ABI (include/ganon.h is).
 //
 // A batch lives in HBM in two layers:
 //   raw      the ganon_batch SoA exactly as the host hands it over (BAM nt16 bases, BAM CIGAR
@@ -27,7 +27,9 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kTile = 16384;           // positions per tile of a huge scope (tile path)
 
-// ---- group kernels (ganon_hip.hip k_group) -----------------------------------------------
+// ---- group kernels (ganon_group.hip k_group) ---------------------------------------------
+// GANON_PARAM_GROUP_SKIP (profiling only, results invalid): phases left out
+enum { kSkipClassify = 1, kSkipChunks = 2, kSkipCopy = 4, kSkipCounts = 8 };
 constexpr int kGrpRec = 5;             // int4 records per group (layout below)
 constexpr int kGrpObs = 512;           // observations per LDS list
 constexpr int kGrpMaxScopes = 256;     // scopes per group (8-bit LDS counters index, 12-bit field)
@@ -136,8 +138,56 @@ enum PrepErrKind {
   kErrScopeOff, kErrScopeSpan, kErrScopeRef, kErrScopeKeep, kErrIncidRead, kErrIncidSpan, kErrWriteScopeMissing
 };
 
-// ---- device helpers shared by the prep kernels (ganon_prep.hip) and the group kernels
+// ---- device helpers shared by the prep kernels (ganon_prep.hip), the group kernels
+// (ganon_group.hip), the huge-scope tile path (ganon_huge.hip) and k_ref2 (ganon_hip.hip)
 #ifdef __HIPCC__
+// Buffers reached through GrpAux (device memory holding pointers) as address-space-1 pointers:
+// global_* memory ops instead of flat_* on the overflow, far-list and per-scope-count paths.
+template <class T>
+__device__ __forceinline__ __attribute__((address_space(1))) T *gp(T *p) {
+  return (__attribute__((address_space(1))) T *)(uintptr_t)p;
+}
+typedef __attribute__((address_space(1))) unsigned long long GU64;
+typedef __attribute__((address_space(1))) unsigned int GU32;
+
+__device__ __forceinline__ int nib_at(const uint8_t *__restrict__ buf, int64_t i) {
+  const uint8_t b = buf[i >> 1];
+  return (i & 1) ? (b & 0xF) : (b >> 4);
+}
+
+__device__ __forceinline__ bool is_acgt(int c) { return c != 0 && (c & (c - 1)) == 0 && c <= 8; }
+
+__device__ __forceinline__ uint32_t nib_swap(uint32_t d) { return ((d >> 4) & 0x0F0F0F0Fu) | ((d & 0x0F0F0F0Fu) << 4); }
+
+// 16 consecutive nibbles starting at nibble index n of a packed buffer (padded by 12 bytes):
+// nibble k of the result at bits [4k, 4k+4).
+__device__ __forceinline__ uint64_t load16(const uint8_t *__restrict__ buf, int64_t n) {
+  const uint32_t *p = reinterpret_cast<const uint32_t *>(buf) + (n >> 3);
+  const uint32_t d0 = nib_swap(p[0]), d1 = nib_swap(p[1]), d2 = nib_swap(p[2]);
+  const uint64_t x0 = (uint64_t)d0 | ((uint64_t)d1 << 32);
+  const uint64_t x1 = (uint64_t)d1 | ((uint64_t)d2 << 32);
+  const int sh = 4 * (int)(n & 7);
+  return (uint64_t)(uint32_t)(x0 >> sh) | ((uint64_t)(uint32_t)(x1 >> sh) << 32);
+}
+
+// 16 codes of a 2-bit window (k_ref2: code k at bits 2k) as one-hot nt16 nibbles (nibble k).
+__device__ __forceinline__ uint64_t expand2(uint32_t x) {
+  uint64_t y = x;
+  y = (y | (y << 16)) & 0x0000FFFF0000FFFFull;
+  y = (y | (y << 8)) & 0x00FF00FF00FF00FFull;
+  y = (y | (y << 4)) & 0x0F0F0F0F0F0F0F0Full;
+  y = (y | (y << 2)) & 0x3333333333333333ull;        // code k in nibble k
+  const uint64_t lo = y & 0x1111111111111111ull, hi = (y >> 1) & 0x1111111111111111ull;
+  const uint64_t v = lo + 0x1111111111111111ull;     // 1 (A) or 2 (C) ...
+  const uint64_t m = hi * 15;                         // ... shifted to 4 (G) or 8 (T)
+  return (v & ~m) | ((v << 2) & m);
+}
+
+__device__ __forceinline__ int64_t i64_of(int lo, int hi) {
+  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
+}
+
+
 __device__ __forceinline__ void report(PrepErr *err, int kind, long long index, long long a = 0, long long b = 0) {
   if (atomicCAS(&err->code, 0, kind) == 0) {
     err->index = index;
@@ -232,11 +282,11 @@ struct ganon_dbatch {
   int64_t max_scope_incid = 0;                                     // most incidences of one scope (host, at load)
   bool ordered = false;                                            // the run launches groups in b_order's order
   ganon_dev::DBuf b_read_end, b_cursor, b_gs0, b_lo, b_linemap, b_groups, b_seg4, b_grp_part, b_far, b_gokey, b_gopay, b_gtkey, b_gtflag, b_out,
-      b_scope_calls, b_scope_bases, b_small;   // b_small: totals, static totals, counters, acc, status, errors
+      b_scope_calls, b_scope_bases, b_small;   // b_small: totals, static totals, rare-tile count, acc, status, errors
   uint8_t *out = nullptr;
   int32_t *scope_calls = nullptr, *scope_bases = nullptr;
   unsigned long long *totals = nullptr, *static_totals = nullptr, *acc = nullptr, *far_count = nullptr;
-  int32_t *counters = nullptr;          // [0] rare small (unused), [1] rare tiles
+  int32_t *rare_tiles = nullptr;        // tiles of huge scopes that met a non-ACGTN base (k_tile_large; k_finish resets it)
   int32_t *status = nullptr;            // device status bits of the run (1: far-mask list overflow, 2: write-scope
                                         // sums, 4: gated by the plan); cleared with the other flags per plan
   unsigned int *long_count = nullptr;   // reads the scan left to k_prep_scan_long
@@ -325,6 +375,29 @@ inline int grow_n(ganon_ctx *ctx, ganon_dev::DBuf &b, size_t count, T **out) {
 }
 
 }  // namespace ganon_prep
+
+namespace ganon_group {   // ganon_group.hip
+
+// Is a k_group instantiation compiled for this record source, unroll and observation-list size?
+bool compiled(bool fused, bool long_mode, int unroll, int obs);
+// Launch the group kernel over db's groups (async on the stream). ref2: the 2-bit reference, or null
+// when the run reads the nt16 reference only (GANON_PARAM_REF2).
+int launch(ganon_ctx *ctx, ganon_dbatch *db, int unroll, int obs, const uint32_t *ref2);
+
+}  // namespace ganon_group
+
+namespace ganon_huge {   // ganon_huge.hip: scopes wider than kGrpMaxSpan (tile path)
+
+// Once per context: the tile kernels' dynamic LDS sizes.
+void init();
+// Plan db's huge scopes from the host batch b: tiles, their reads, the table offsets (async uploads).
+int plan(ganon_ctx *ctx, ganon_dbatch *db, const ganon_batch *b);
+// Free what plan and run allocated.
+void release(ganon_dbatch *db);
+// Tally the tiles and write the reads of the huge scopes (async on the stream; nothing without tiles).
+int run(ganon_ctx *ctx, ganon_dbatch *db);
+
+}  // namespace ganon_huge
 
 // Non-ACGT block bitmap of a resident reference (ganon_prep.hip), async on the stream.
 int ganon_ref_blocks(ganon_ctx *ctx, ganon_ref *ref);

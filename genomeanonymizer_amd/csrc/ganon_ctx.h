@@ -1,5 +1,5 @@
 // ganon_ctx.h — internal to libganon_hip.so: the context shared by the masking kernels
-// (ganon_hip.hip) and the FASTQ formatter (ganon_fastq.hip), error/launch helpers and the
+// (ganon_hip.hip, ganon_group.hip, ganon_huge.hip) and the FASTQ formatter (ganon_fastq.hip), error/launch helpers and the
 // per-kernel event timer. Not part of the C ABI (include/ganon.h is).
 #ifndef GANON_CTX_H
 #define GANON_CTX_H
@@ -34,7 +34,6 @@ struct ganon_ctx {
   hipStream_t own = nullptr;
   hipStream_t stream = nullptr;
   bool profiling = false;
-  int variant = GANON_VARIANT_DEFAULT;
   int group_unroll = 0;        // GANON_PARAM_GROUP_UNROLL (0 auto: 1 for long reads, else 2)
   int group_skip = 0;          // GANON_PARAM_GROUP_SKIP (profiling only)
   int group_target = 0;        // GANON_PARAM_GROUP_TARGET (0 auto: 704 short reads, 2816 long-read mode), cost units per group (segments + a

@@ -8,7 +8,7 @@
 // the read only, deletions and skips the reference only (variation_classifier.py:185-215 walks
 // those columns). Here each read's CIGAR is walked once per (scope, read) incidence into segment
 // records — one per aligned run: (query nibble, reference nibble, length, dataset, whether this
-// scope writes the read) — that k_group (ganon_hip.hip) streams in 16-base chunks.
+// scope writes the read) — that k_group (ganon_group.hip) streams in 16-base chunks.
 //
 // Kernels (integer work, HBM/latency bound, no MFMA), in launch order. Plan (ganon_batch_replan /
 // the upload; one host synchronization):

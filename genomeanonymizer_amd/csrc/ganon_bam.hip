@@ -33,6 +33,12 @@
 // writes the name blob: a workgroup's 256 names are one contiguous 8,448-byte range, built in LDS and
 // stored as coalesced dwords. Without a key nothing of this runs: the sizes and scatter kernels are
 // the instantiations they were.
+//
+// Known sites (--known_sites, ganon_ctx_set_known_sites). With a panel table on the context
+// k_bam_known_mask runs after the scatter over the columns in device memory: a base aligned to a listed
+// position that shows a listed ALT becomes the reference base (ganon_known_sites.h, the host decoder's
+// rule). A thread per record — almost all leave after one lower bound —, a wave per record with more
+// than 48 CIGAR ops. Without a table nothing of this runs.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
@@ -495,6 +501,107 @@ __global__ void __launch_bounds__(kBamThreads) k_bam_name_hash(const uint8_t *__
   if ((int)threadIdx.x < (bytes & 3)) out[(bytes & ~3) + threadIdx.x] = (char)sb[(bytes & ~3) + threadIdx.x];
 }
 
+constexpr int kKsLongOps = 48;   // records with more CIGAR ops take a wave each (the scan's threshold)
+
+// Inclusive prefix sum over the wave of values below 2^28 (CIGAR op lengths) without overflow: the low
+// and the high 14 bits summed apart (64 x 2^14 fits an int), wave total in `total`.
+__device__ __forceinline__ int64_t ks_incl_sum(uint32_t v, int64_t &total) {
+  const int lo = ganon_wave::incl_sum((int)(v & 0x3FFFu)), hi = ganon_wave::incl_sum((int)(v >> 14));
+  total = (int64_t)ganon_wave::last(lo) + ((int64_t)ganon_wave::last(hi) << 14);
+  return (int64_t)lo + ((int64_t)hi << 14);
+}
+
+// One record with a long CIGAR, by one wave (every lane active): 64 ops at a time, their reference and
+// query starts from prefix sums; a lane with an M / = / X op searches the sites inside its op's
+// reference range and patches them. Two lanes can own the two nibbles of one byte (an op boundary at
+// an odd query index), so a nibble is rewritten by a 32-bit atomic xor of (base ^ ref) on the aligned
+// word that holds it (the blobs are 256-byte aligned and padded): no lane writes a bit it does not own.
+__device__ __forceinline__ int ks_mask_wave(const ganon_ks::View &S, int lane, int32_t tid, int32_t pos, int32_t ncig,
+                                            int32_t lseq, const uint32_t *__restrict__ cig, uint8_t *seq, uint8_t *qual) {
+  const int64_t lo = S.off[tid], hi = S.off[tid + 1];
+  if (ganon_ks::lower(S.pos, lo, hi, pos) >= hi) return 0;   // (wave-uniform)
+  const bool q_on = S.qual >= 0 && qual[0] != 0xFF;
+  int64_t r = pos, q = 0;
+  int cnt = 0;
+  for (int k0 = 0; k0 < ncig && q < lseq; k0 += 64) {
+    const uint32_t w = k0 + lane < ncig ? cig[k0 + lane] : 0u;
+    const int op = (int)(w & 15u);
+    const uint32_t len = w >> 4;
+    const bool m = op == 0 || op == 7 || op == 8;
+    const uint32_t rl = (m || op == 2 || op == 3) ? len : 0u, ql = (m || op == 1 || op == 4) ? len : 0u;
+    int64_t rt, qt;
+    const int64_t r0 = r + ks_incl_sum(rl, rt) - rl, q0 = q + ks_incl_sum(ql, qt) - ql;
+    if (m && len && q0 < lseq) {
+      const int64_t rend = r0 + len;
+      for (int64_t j = ganon_ks::lower(S.pos, lo, hi, r0); j < hi; ++j) {
+        const int64_t p = S.pos[j];
+        if (p >= rend) break;
+        const int64_t x = q0 + (p - r0);
+        if (x >= lseq) break;
+        const uint8_t code = S.code[j];
+        const int sh = (x & 1) ? 0 : 4;
+        const int b = (seq[x >> 1] >> sh) & 15;
+        if (ganon_ks::hits(b, code)) {
+          const uintptr_t a = reinterpret_cast<uintptr_t>(seq + (x >> 1));
+          __hip_atomic_fetch_xor(reinterpret_cast<uint32_t *>(a & ~(uintptr_t)3),
+                                 (uint32_t)(b ^ (code >> 4)) << (8 * (int)(a & 3) + sh), __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+          if (q_on) qual[x] = (uint8_t)S.qual;
+          ++cnt;
+        }
+      }
+    }
+    r += rt;
+    q += qt;
+  }
+  return cnt;
+}
+
+// The panel mask of --known_sites over the decoded columns (ganon_known_sites.h has the rule). A thread
+// per record: its columns, then a lower bound of pos in its sequence's sites; no site before `end`
+// (almost every short read at panel densities) and it is done, else it merge-walks its CIGAR and the
+// sites (ganon_ks::mask_record; its bases are whole bytes it alone owns: plain byte stores). Records
+// with more than kKsLongOps ops are listed in LDS instead and taken a wave each (ks_mask_wave). One
+// atomic add per workgroup that rewrote anything.
+__global__ void __launch_bounds__(kBamThreads) k_bam_known_mask(ganon_bam_cols V, int64_t nr, ganon_ks::View S,
+                                                                unsigned long long *__restrict__ count) {
+  __shared__ int s_long[kBamThreads];
+  __shared__ int s_nlong, s_cnt;
+  if (threadIdx.x == 0) s_nlong = s_cnt = 0;
+  __syncthreads();
+  const int64_t i0 = (int64_t)blockIdx.x * kBamThreads;
+  const int64_t i = i0 + threadIdx.x;
+  int cnt = 0;
+  if (i < nr) {
+    const int32_t tid = V.tid[i], pos = V.pos[i], end = V.end[i], flag = V.flag[i], ncig = V.n_cigar[i], lseq = V.l_seq[i];
+    const int64_t o_cig = V.cig_off[i], o_seq = V.seq_off[i], o_qual = V.qual_off[i];
+    if (!ganon_ks::skips(S, tid, (uint32_t)flag, ncig, lseq)) {
+      const int64_t hi = S.off[tid + 1];
+      const int64_t j = ganon_ks::lower(S.pos, S.off[tid], hi, pos);
+      if (j < hi && S.pos[j] < end) {
+        if (ncig > kKsLongOps)
+          s_long[atomicAdd(&s_nlong, 1)] = (int)threadIdx.x;
+        else
+          cnt = ganon_ks::mask_record(S, tid, pos, (uint32_t)flag, ncig, lseq, V.cigar + o_cig, V.seq + o_seq, V.qual + o_qual);
+      }
+    }
+  }
+  __syncthreads();
+  const int nlong = s_nlong, lane = threadIdx.x & 63;
+  for (int k = threadIdx.x >> 6; k < nlong; k += kBamThreads / 64) {   // (wave-uniform)
+    const int64_t g = i0 + s_long[k];
+    const int c = ks_mask_wave(S, lane, V.tid[g], V.pos[g], V.n_cigar[g], V.l_seq[g], V.cigar + V.cig_off[g],
+                               V.seq + V.seq_off[g], V.qual + V.qual_off[g]);
+    cnt += c;
+  }
+  if (__any(cnt != 0)) {
+    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_xor(cnt, s);
+    if (lane == 0) atomicAdd(&s_cnt, cnt);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_cnt) atomicAdd(count, (unsigned long long)s_cnt);
+}
+
 unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBamThreads - 1) / kBamThreads); }
 
 template <typename T>
@@ -756,6 +863,13 @@ int columns(ganon_ctx *ctx, const uint8_t *d, int64_t p, int64_t n, ganon_bam_dc
     }
     if ((rc = check_launch(ctx, "k_bam_name_hash"))) return rc;
   }
+  if (nr && ctx->ks_block) {   // --known_sites: the panel mask over the columns just written
+    {
+      ganon_detail::KernelScope ks(ctx, "k_bam_known_mask");
+      hipLaunchKernelGGL(k_bam_known_mask, dim3(grid_of(nr)), dim3(kBamThreads), 0, s, V, nr, ctx->ks_view, ctx->ks_count);
+    }
+    if ((rc = check_launch(ctx, "k_bam_known_mask"))) return rc;
+  }
   return ganon_batch_sync(ctx);   // (collects the kernel times when profiling)
 }
 
@@ -818,6 +932,78 @@ GANON_API int ganon_ctx_set_name_key(ganon_ctx *ctx, const uint8_t *key, int32_t
   ctx->name_hash = key_len > 0;
   if (ctx->name_hash) ganon_nh::key_state(key, key_len, &ctx->name_key);
   return GANON_OK;
+}
+
+// The running count of the table in place, added to ks_total; the device counter is left as it is.
+static int ks_collect(ganon_ctx *ctx, int64_t *sum) {
+  *sum = ctx->ks_total;
+  if (!ctx->ks_block) return GANON_OK;
+  unsigned long long c = 0;
+  HIP_OR_FAIL(ganon_detail::readback(&c, ctx->ks_count, 8, ctx->stream));
+  HIP_OR_FAIL(ganon_detail::sync_stream(ctx->stream));
+  *sum += (int64_t)c;
+  return GANON_OK;
+}
+
+GANON_API int ganon_ctx_set_known_sites(ganon_ctx *ctx, int32_t n_ref, const int64_t *site_off, const int32_t *site_pos,
+                                        const uint8_t *site_code, int64_t n, int32_t quality) {
+  if (!ctx) return GANON_E_ARG;
+  if (n < 0 || quality < -1 || quality > 93 || (n > 0 && (n_ref <= 0 || !site_off || !site_pos || !site_code)))
+    return fail(ctx, GANON_E_ARG, "ganon_ctx_set_known_sites: bad arguments");
+  if (n > 0) {   // (the kernel trusts the table: what ganon_sites_create checks)
+    if (site_off[0] != 0 || site_off[n_ref] != n)
+      return fail(ctx, GANON_E_ARG, "ganon_ctx_set_known_sites: site_off must run from 0 to n");
+    for (int32_t t = 0; t < n_ref; ++t) {
+      if (site_off[t + 1] < site_off[t] || site_off[t + 1] > n)
+        return fail(ctx, GANON_E_ARG, "ganon_ctx_set_known_sites: site_off must not decrease");
+      for (int64_t j = site_off[t]; j < site_off[t + 1]; ++j)
+        if (site_pos[j] < 0 || (j > site_off[t] && site_pos[j] <= site_pos[j - 1]) || !ganon_ks::code_ok(site_code[j]))
+          return fail(ctx, GANON_E_ARG, "ganon_ctx_set_known_sites: site %lld: positions strictly increasing per sequence, "
+                      "codes ref_nt16 << 4 | alt_mask", (long long)j);
+    }
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
+  if (ctx->ks_block) {   // the table in place goes: its count stays in the total
+    int64_t sum = 0;
+    const int rc = ks_collect(ctx, &sum);
+    if (rc) return rc;
+    ctx->ks_total = sum;
+    HIP_OR_FAIL(hipFree(ctx->ks_block));   // (waits for the device: no kernel reads it any more)
+    ctx->ks_block = nullptr;
+    ctx->ks_count = nullptr;
+    ctx->ks_view = ganon_ks::View{};
+  }
+  if (n == 0) return GANON_OK;
+  const int64_t b_off = ((int64_t)(n_ref + 1) * 8 + 255) / 256 * 256, b_pos = (n * 4 + 255) / 256 * 256,
+                b_code = (n + 255) / 256 * 256;
+  void *blk = nullptr;
+  HIP_OR_FAIL(hipMalloc(&blk, (size_t)(b_off + b_pos + b_code + 256)));
+  uint8_t *at = static_cast<uint8_t *>(blk);
+  hipStream_t s = ctx->stream;
+  const unsigned long long zero = 0;
+  if (hipMemcpyAsync(at, site_off, (size_t)(n_ref + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(at + b_off, site_pos, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(at + b_off + b_pos, site_code, (size_t)n, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(at + b_off + b_pos + b_code, &zero, 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+      ganon_detail::sync_stream(s) != hipSuccess) {
+    ganon_detail::sync_stream(s);
+    hipFree(blk);
+    return fail(ctx, GANON_E_DEVICE, "ganon_ctx_set_known_sites: upload failed");
+  }
+  ctx->ks_block = blk;
+  ctx->ks_view.n_ref = n_ref;
+  ctx->ks_view.off = reinterpret_cast<const int64_t *>(at);
+  ctx->ks_view.pos = reinterpret_cast<const int32_t *>(at + b_off);
+  ctx->ks_view.code = at + b_off + b_pos;
+  ctx->ks_view.qual = quality;
+  ctx->ks_count = reinterpret_cast<unsigned long long *>(at + b_off + b_pos + b_code);
+  return GANON_OK;
+}
+
+GANON_API int ganon_ctx_known_sites_masked(ganon_ctx *ctx, int64_t *masked) {
+  if (!ctx || !masked) return fail(ctx, GANON_E_ARG, "ganon_ctx_known_sites_masked: bad arguments");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
+  return ks_collect(ctx, masked);
 }
 
 GANON_API int ganon_bam_dcols_get(const ganon_bam_dcols *c, ganon_bam_cols *device_view, int64_t *fixes) {

@@ -18,6 +18,7 @@
 
 #include "../../include/ganon.h"
 #include "ganon_name_hash.h"
+#include "ganon_known_sites.h"
 
 struct ganon_inflate_state;                       // ganon_inflate.hip: grow-only device buffers
 void ganon_inflate_free(ganon_inflate_state *st);
@@ -69,6 +70,12 @@ struct ganon_ctx {
   ganon_deflate_state *deflate = nullptr;   // BGZF deflate buffers (first ganon_deflate_bgzf)
   bool name_hash = false;                   // ganon_ctx_set_name_key: the BAM decoder hashes the read names
   ganon_nh::KeyState name_key{};
+  // ganon_ctx_set_known_sites: the panel table in device memory (one block: off, pos, code, the count)
+  // and the view k_bam_known_mask takes; ks_block == nullptr: no table, no kernel
+  void *ks_block = nullptr;
+  ganon_ks::View ks_view{};
+  unsigned long long *ks_count = nullptr;   // (device) bases rewritten since the table was set
+  int64_t ks_total = 0;                     // ... and by the tables this context held before
   // GANON_INDEL_FORK=1: the indel tally of a batch runs on a side stream forked after the batch's
   // prep (fork_ev, recorded by ganon_batch_run before the group kernel) and joined back (join_ev), so
   // that its latency-bound launches overlap the bandwidth-bound group kernel (they read only the

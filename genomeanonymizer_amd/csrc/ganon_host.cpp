@@ -20,6 +20,7 @@
 
 #include "../../include/ganon_host.h"
 #include "ganon_name_hash.h"
+#include "ganon_known_sites.h"
 
 namespace {
 
@@ -177,6 +178,7 @@ struct ganon_bam {
   void *ext_block = nullptr;
   ganon_buf_free_fn ext_free = nullptr;
   ganon_bam_view ext{};
+  int64_t known_masked = 0;   // --known_sites: bases records_to_columns rewrote in this table
   ganon_bam() = default;
   ganon_bam(const ganon_bam &) = delete;
   ganon_bam &operator=(const ganon_bam &) = delete;
@@ -191,6 +193,18 @@ static int set_err(const std::string &m) {
 }
 
 GANON_HOST_API const char *ganon_host_last_error(void) { return g_err.c_str(); }
+
+// --known_sites: a panel table, shared by the handle and every reader it was set on (so the handle may
+// be destroyed while a reader still decodes with it).
+struct SitesData {
+  std::vector<int64_t> off;
+  std::vector<int32_t> pos;
+  std::vector<uint8_t> code;
+  ganon_ks::View view;
+};
+struct ganon_sites {
+  std::shared_ptr<const SitesData> data;
+};
 
 namespace {
 
@@ -285,8 +299,12 @@ int parse_header(const uint8_t *d, int64_t n, ganon_bam *bam, int64_t &p) {
 // their records stay in place in the scan's buffer, no boundary walk and no copy of the kept runs).
 // With ks (--hash_read_names) every name is replaced, here where it enters the table, by its keyed
 // hash: 32 hex characters and a NUL, name_off[i] = 33 i; the hash runs on the name pass's threads.
+// With sites (--known_sites) the panel mask (ganon_known_sites.h) rewrites each record's bases, and
+// with a quality their quality bytes, in the table right after they are copied, on the same threads;
+// bam->known_masked counts the rewritten bases.
 int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, int threads,
-                       const std::vector<int64_t> *known = nullptr, const ganon_nh::KeyState *ks = nullptr) {
+                       const std::vector<int64_t> *known = nullptr, const ganon_nh::KeyState *ks = nullptr,
+                       const ganon_ks::View *sites = nullptr) {
   const int nt = std::max(1, std::min(threads, 64));
   // ---- records: boundaries (sequential), sizes + offsets, then columns in parallel ----
   std::vector<int64_t> own;   // offset of each record's block_size field
@@ -356,7 +374,9 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
   huge_resize(bam->qual, (size_t)o_qual[nr]);
   huge_resize(bam->aux, (size_t)o_aux[nr]);
   lap(kPhSizes, tph);
+  std::atomic<int64_t> masked{0};
   run_chunks([&](int64_t i0, int64_t i1) {
+    int64_t mine = 0;
     for (int64_t i = i0; i < i1; ++i) {
       const uint8_t *r = d + rec[i] + 4;
       int32_t bs, rtid, rpos, mtid, mpos, rtlen, lseq;
@@ -414,8 +434,13 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
       bam->aux_off[i] = o_aux[i];
       bam->aux_len[i] = (int32_t)(bs - q);
       copy_bytes(bam->aux.data() + o_aux[i], r + q, (size_t)(bs - q));
+      if (sites)
+        mine += ganon_ks::mask_record(*sites, rtid, rpos, rflag, ncig, lseq, cg, bam->seq.data() + o_seq[i],
+                                      bam->qual.data() + o_qual[i]);
     }
+    if (mine) masked.fetch_add(mine, std::memory_order_relaxed);
   });
+  bam->known_masked += masked.load();
   lap(kPhColumns, tph);
   return 0;
 }
@@ -423,7 +448,8 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
 
 }  // namespace
 
-static int bam_open_impl(const char *path, int threads, ganon_bam **out, const ganon_nh::KeyState *ks = nullptr) {
+static int bam_open_impl(const char *path, int threads, ganon_bam **out, const ganon_nh::KeyState *ks = nullptr,
+                         const ganon_ks::View *sites = nullptr) {
   FILE *fh = std::fopen(path, "rb");
   if (!fh) return set_err(std::string("cannot open ") + path);
   std::fseek(fh, 0, SEEK_END);
@@ -460,7 +486,7 @@ static int bam_open_impl(const char *path, int threads, ganon_bam **out, const g
     delete bam;
     return hr < 0 ? -1 : set_err("truncated header");
   }
-  if (records_to_columns(data.data(), p, (int64_t)data.size(), bam, threads, nullptr, ks) != 0) {
+  if (records_to_columns(data.data(), p, (int64_t)data.size(), bam, threads, nullptr, ks, sites) != 0) {
     delete bam;
     return -1;
   }
@@ -497,6 +523,61 @@ GANON_HOST_API int ganon_bam_open_keyed(const char *path, int threads, const uin
     return set_err(std::string("BAM decode failed: ") + e.what());
   }
 }
+
+GANON_HOST_API int ganon_sites_create(int32_t n_ref, const int64_t *site_off, const int32_t *site_pos,
+                                      const uint8_t *site_code, int32_t quality, ganon_sites **out) {
+  if (!out) return set_err("null argument");
+  *out = nullptr;
+  if (n_ref < 0 || !site_off || quality < -1 || quality > 93) return set_err("ganon_sites_create: bad arguments");
+  if (site_off[0] != 0) return set_err("ganon_sites_create: site_off[0] must be 0");
+  for (int32_t t = 0; t < n_ref; ++t)
+    if (site_off[t + 1] < site_off[t]) return set_err("ganon_sites_create: site_off must not decrease");
+  const int64_t ns = site_off[n_ref];
+  if (ns > 0 && (!site_pos || !site_code)) return set_err("ganon_sites_create: bad arguments");
+  for (int32_t t = 0; t < n_ref; ++t)
+    for (int64_t j = site_off[t]; j < site_off[t + 1]; ++j) {
+      if (site_pos[j] < 0 || (j > site_off[t] && site_pos[j] <= site_pos[j - 1]))
+        return set_err("ganon_sites_create: positions must be >= 0 and strictly increasing per sequence");
+      if (!ganon_ks::code_ok(site_code[j]))
+        return set_err("ganon_sites_create: a code is ref_nt16 << 4 | alt_mask, ref one of 1, 2, 4, 8 and not in alt_mask");
+    }
+  try {
+    auto d = std::make_shared<SitesData>();
+    d->off.assign(site_off, site_off + n_ref + 1);
+    d->pos.assign(site_pos, site_pos + ns);
+    d->code.assign(site_code, site_code + ns);
+    d->view.n_ref = n_ref;
+    d->view.off = d->off.data();
+    d->view.pos = d->pos.data();
+    d->view.code = d->code.data();
+    d->view.qual = quality;
+    *out = new ganon_sites{std::move(d)};
+    return 0;
+  } catch (const std::bad_alloc &) {
+    return set_err("out of memory copying the known-sites table");
+  }
+}
+
+GANON_HOST_API void ganon_sites_destroy(ganon_sites *s) { delete s; }
+
+GANON_HOST_API int ganon_bam_open_ex(const char *path, int threads, const uint8_t *key, int32_t key_len,
+                                     const ganon_sites *sites, ganon_bam **out) {
+  if (!path || !out) return set_err("null argument");
+  *out = nullptr;
+  if (key_len < 0 || key_len > ganon_nh::kMaxKey || (key_len > 0 && !key))
+    return set_err("ganon_bam_open_ex: a key of 1..32 bytes, or length 0 for none");
+  ganon_nh::KeyState ks;
+  if (key_len > 0) ganon_nh::key_state(key, key_len, &ks);
+  try {
+    return bam_open_impl(path, threads, out, key_len > 0 ? &ks : nullptr, sites ? &sites->data->view : nullptr);
+  } catch (const std::bad_alloc &) {
+    return set_err("out of memory decoding the BAM file");
+  } catch (const std::exception &e) {
+    return set_err(std::string("BAM decode failed: ") + e.what());
+  }
+}
+
+GANON_HOST_API int64_t ganon_bam_known_sites_masked(const ganon_bam *b) { return b ? b->known_masked : 0; }
 
 GANON_HOST_API int ganon_names_hash(const char *names, const int64_t *off, const int32_t *len, int64_t n,
                                     const uint8_t *key, int32_t key_len, int threads, char *out) {
@@ -612,6 +693,8 @@ struct ganon_bam_reader {
   ganon_buf_free_fn rdec_release = nullptr;
   bool hashed = false;                   // ganon_bam_reader_set_name_key: names enter the tables hashed
   ganon_nh::KeyState name_key{};
+  std::shared_ptr<const SitesData> sites;   // ganon_bam_reader_set_known_sites: the panel mask of its tables
+  int64_t known_masked = 0;                 // ... and the bases its host decodes rewrote so far
 };
 
 namespace {
@@ -1097,6 +1180,14 @@ GANON_HOST_API int ganon_bam_reader_set_name_key(ganon_bam_reader *R, const uint
   return 0;
 }
 
+GANON_HOST_API int ganon_bam_reader_set_known_sites(ganon_bam_reader *R, const ganon_sites *sites) {
+  if (!R) return set_err("null argument");
+  R->sites = sites ? sites->data : nullptr;
+  return 0;
+}
+
+GANON_HOST_API int64_t ganon_bam_reader_known_sites_masked(const ganon_bam_reader *R) { return R ? R->known_masked : 0; }
+
 GANON_HOST_API int ganon_bam_reader_has_index(const ganon_bam_reader *R) { return R && R->has_index ? 1 : 0; }
 
 GANON_HOST_API int ganon_bam_reader_header(ganon_bam_reader *R, ganon_bam_view *v) {
@@ -1140,10 +1231,12 @@ GANON_HOST_API int ganon_bam_reader_contig(ganon_bam_reader *R, int32_t tid, gan
     bam->ref_names = R->header.ref_names;
     bam->ref_name_off = R->header.ref_name_off;
     bam->ref_len = R->header.ref_len;
-    if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs, R->hashed ? &R->name_key : nullptr) != 0) {
+    if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs, R->hashed ? &R->name_key : nullptr,
+                           R->sites ? &R->sites->view : nullptr) != 0) {
       delete bam;
       return -1;
     }
+    R->known_masked += bam->known_masked;
     *out = bam;
     return 0;
   } catch (const std::bad_alloc &) {
@@ -1200,10 +1293,12 @@ GANON_HOST_API int ganon_bam_reader_region(ganon_bam_reader *R, int32_t tid, int
       *out = bam;
       return 0;
     }
-    if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs, R->hashed ? &R->name_key : nullptr) != 0) {
+    if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs, R->hashed ? &R->name_key : nullptr,
+                           R->sites ? &R->sites->view : nullptr) != 0) {
       delete bam;
       return -1;
     }
+    R->known_masked += bam->known_masked;
     *out = bam;
     return 0;
   } catch (const std::bad_alloc &) {

@@ -2,7 +2,7 @@
 
   python -m genomeanonymizer_amd.genome_anonymizer -d DIR -s samples.tsv -r ref.fa \\
       [-m complete_germline] [-c CPUS] [--record_statistics] [--enhanced_multiprocessing] [-v N]
-      [--compress_output] [--masked_base_quality Q] [--hash_read_names]
+      [--compress_output] [--masked_base_quality Q] [--hash_read_names] [--known_sites PANEL.vcf[.gz]]
 
 samples.tsv: tumor<TAB>normal<TAB>vcf per line, paths relative to DIR, '#' lines skipped.
 Outputs next to the inputs: re.sub('.bam|.sam|.cram', '.anonymized', path) + .1/.2.fastq
@@ -20,6 +20,20 @@ comes from GANON_READ_NAME_KEY (2 to 64 hex digits; there is no key flag: it wou
 it 32 random bytes are drawn once per invocation: the names are then unlinkable and the run cannot be
 repeated. A supplied key makes runs reproducible and must be kept as secret as the original names.
 The key is never logged or written; one key serves every pair of the invocation, tumor and normal.
+--known_sites PANEL.vcf[.gz] (an extension; GANON_KNOWN_SITES=path is the same default): a population
+panel (dbSNP, gnomAD, a cohort's own). The masking rule rewrites a germline SNV only where a tumor and
+a normal read of one pileup scope show it; with a panel, every read base that is aligned (CIGAR M, =, X)
+to a listed position and shows a listed one-base ALT allele becomes the reference base where its
+record is decoded, in every read that reaches any output, in a scope or not. The run writes exactly
+what a run without the option writes on BAMs rewritten that way. Lines with REF one of A, C, G, T and a
+one-base ALT are used (the other ALTs of such a line are ignored), lines with a longer REF (indels,
+MNVs) are skipped and counted, contigs absent from the BAM header are ignored. REF must be the FASTA's
+base: a mismatch, two REFs at one position, a position past the contig's end or an unreadable file end
+the run before any output file is opened. The positions of each pair's own VCF SNVs are left out of
+the panel for that pair: those calls are what the product keeps. With --masked_base_quality Q the
+rewritten bases are printed with quality Q too. Limits: a supplementary record is masked along its own
+alignment, the primary's soft-clipped copy of those bases is not; indels and MNVs of the panel are not
+used. Each process logs how many bases it rewrote.
 
 Multi-GPU: launch under ``torchrun --nproc-per-node N`` (or set WORLD_SIZE/RANK/LOCAL_RANK):
 contigs are sharded round-robin over the ranks; each rank decodes, masks and writes its own
@@ -69,6 +83,9 @@ def exec_parser(argv=None):
     parser.add_argument("--hash_read_names", action=BooleanOptionalAction,
                         help="Replace every read name by its keyed BLAKE2s-128 hash, 32 hex characters (default: "
                              "GANON_HASH_READ_NAMES; key: GANON_READ_NAME_KEY as hex, else random per invocation)")
+    parser.add_argument("--known_sites", type=str, metavar="PANEL.vcf[.gz]", default=None,
+                        help="Population panel: read bases showing a listed one-base ALT at a listed position "
+                             "become the reference base where the record is decoded (default: GANON_KNOWN_SITES)")
     parser.add_argument("-v", "--verbose", type=int, required=False, default=2, help="Verbosity of logging")
     parser.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     return parser.parse_args(argv)
@@ -108,6 +125,8 @@ def run_anonymizer(argv=None) -> None:
         os.environ["GANON_MASKED_BASE_QUALITY"] = str(config.masked_base_quality)
     if config.hash_read_names is not None:
         os.environ["GANON_HASH_READ_NAMES"] = "1" if config.hash_read_names else "0"
+    if config.known_sites is not None:
+        os.environ["GANON_KNOWN_SITES"] = config.known_sites
     from . import native
     try:   # (a malformed key ends the run here, before any file is opened)
         if os.environ.get("GANON_HASH_READ_NAMES", "0") == "1" and native.NAME_KEY_ENV in os.environ:
@@ -116,6 +135,14 @@ def run_anonymizer(argv=None) -> None:
         logging.error("%s", e)
         sys.exit(1)
     vcfs, samples, outputs = read_samples(join_dir_file(config.directory, config.samples), config.directory)
+    if os.environ.get("GANON_KNOWN_SITES"):   # (a panel that cannot be used ends the run here, too)
+        from .io.fasta import FastaRef
+        from .known_sites import panel_default
+        try:
+            panel_default(FastaRef(config.reference))
+        except native.GanonError as e:
+            logging.error("%s", e)
+            sys.exit(1)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))

@@ -60,16 +60,30 @@ def _view(ptr, n, dtype, owner: _Decoded):
 class ReadTable:
     """All records of one BAM file, in file order."""
 
-    def __init__(self, path: str, threads: int = 8, handle=None, name_key: Optional[bytes] = None):
+    def __init__(self, path: str, threads: int = 8, handle=None, name_key: Optional[bytes] = None,
+                 known_sites=None):
         """Decode the whole file, or take the records of an open ``ganon_bam`` handle (one
         reference sequence from ``BamReader.contig``); the table owns the handle from here on.
         ``name_key`` (--hash_read_names): every name is replaced, as it is decoded, by
         hex(BLAKE2s(name, key, digest_size=16)) (``ganon_bam_open_keyed``); a handle's names are
-        whatever its reader decoded."""
+        whatever its reader decoded. ``known_sites`` (--known_sites; a known_sites.SitesTable, or a
+        PairPanel that makes the table of this file's header): the panel mask rewrites the bases as they
+        are decoded (``ganon_bam_open_ex``); ``known_masked`` counts them."""
         lib = native.host_lib()
         if handle is None:
             h = C.c_void_p()
-            if name_key:
+            if known_sites is not None:
+                from ..known_sites import resolve
+                if hasattr(known_sites, "table"):   # (the table goes by sequence id: the header first)
+                    hdr = BamReader(path, threads=1)
+                    try:
+                        known_sites = resolve(known_sites, hdr.ref_names)
+                    finally:
+                        hdr.close()
+                self.known_sites = known_sites   # (kept: the decode below reads its arrays)
+                key = bytes(name_key or b"")
+                rc = lib.ganon_bam_open_ex(os.fsencode(path), int(threads), key, len(key), known_sites.handle, C.byref(h))
+            elif name_key:
                 rc = lib.ganon_bam_open_keyed(os.fsencode(path), int(threads), bytes(name_key), len(name_key), C.byref(h))
             else:
                 rc = lib.ganon_bam_open(os.fsencode(path), int(threads), C.byref(h))
@@ -81,6 +95,7 @@ class ReadTable:
         v = native.BamView()
         lib.ganon_bam_view_get(h, C.byref(v))
         self._load(path, v, owner)
+        self.known_masked = int(lib.ganon_bam_known_sites_masked(h))
         self._finish()
 
     def _load(self, path: str, v, owner: _Decoded) -> None:
@@ -256,10 +271,13 @@ class BamReader:
     through ``<bam>.bai`` when present, else streams forward. ``inflater``: a native.GpuInflater
     that inflates the reader's BGZF block windows instead of its zlib threads. ``name_key``
     (--hash_read_names): every table carries hashed names (``ganon_bam_reader_set_name_key``), and an
-    inflater set on the reader hashes with the same key on the device (``GpuInflater.set_name_key``)."""
+    inflater set on the reader hashes with the same key on the device (``GpuInflater.set_name_key``).
+    ``known_sites`` (--known_sites; a known_sites.SitesTable, or a PairPanel that makes the table of
+    this file's header): every table is masked by the panel (``ganon_bam_reader_set_known_sites``), and
+    an inflater set on the reader holds the same table on the device (``GpuInflater.set_known_sites``)."""
 
     def __init__(self, path: str, threads: int = 8, window: int = 0, inflater=None,
-                 name_key: Optional[bytes] = None):
+                 name_key: Optional[bytes] = None, known_sites=None):
         lib = native.host_lib()
         h = C.c_void_p()
         rc = lib.ganon_bam_reader_open(os.fsencode(path), int(threads), C.byref(h))
@@ -275,8 +293,8 @@ class BamReader:
         if window:
             lib.ganon_bam_reader_set_window(h, int(window))
         self.inflater = None
-        if inflater is not None:
-            self.set_inflater(inflater)
+        self.known_sites = None
+        self._dev_masked0 = 0
         v = native.BamView()
         lib.ganon_bam_reader_header(h, C.byref(v))
         off = _arr(v.ref_name_off, v.n_ref, np.int64)
@@ -284,6 +302,15 @@ class BamReader:
         self.ref_names: List[str] = [C.string_at(raw + int(o)).decode() for o in off]
         self.ref_lens = _arr(v.ref_len, v.n_ref, np.int64)
         self.has_index = bool(lib.ganon_bam_reader_has_index(h))
+        if known_sites is not None:
+            from ..known_sites import resolve
+            self.known_sites = resolve(known_sites, self.ref_names)
+            if lib.ganon_bam_reader_set_known_sites(h, self.known_sites.handle) != 0:
+                msg = lib.ganon_host_last_error().decode()
+                self.close()
+                raise native.GanonError(msg)
+        if inflater is not None:
+            self.set_inflater(inflater)
 
     def set_inflater(self, inflater) -> None:
         """Block windows inflate on the GPU from now on (a native.GpuInflater, kept alive here: the
@@ -293,6 +320,11 @@ class BamReader:
             inflater.set_name_key(self.name_key)
         elif self.name_key:
             raise native.GanonError("this inflater cannot hash read names (no set_name_key)")
+        if hasattr(inflater, "set_known_sites"):
+            inflater.set_known_sites(self.known_sites)   # (set or cleared on every attach, as the key)
+            self._dev_masked0 = inflater.known_sites_masked() if self.known_sites is not None else 0
+        elif self.known_sites is not None:
+            raise native.GanonError("this inflater cannot mask known sites (no set_known_sites)")
         native.host_lib().ganon_bam_reader_set_inflater(self._h, inflater.fn, inflater.handle, inflater.min_blocks)
         self.inflater = inflater
         if isinstance(inflater, native.GpuInflater) and os.environ.get("GANON_PINNED_SCAN", "1") != "0":
@@ -307,6 +339,14 @@ class BamReader:
                 native.host_lib().ganon_bam_reader_set_region_decoder(
                     self._h, inflater.region_fn, inflater.handle, inflater.min_blocks,
                     C.cast(hl.ganon_pinned_free, C.c_void_p))
+
+    def known_masked(self) -> int:
+        """--known_sites: bases rewritten in this reader's tables so far, by its host decodes
+        (``ganon_bam_reader_known_sites_masked``) and, since it was attached, by its inflater's context."""
+        n = int(native.host_lib().ganon_bam_reader_known_sites_masked(self._h)) if self._h else 0
+        if self.known_sites is not None and self.inflater is not None and hasattr(self.inflater, "known_sites_masked"):
+            n += self.inflater.known_sites_masked() - self._dev_masked0
+        return n
 
     def tid_of(self, contig: str) -> int:
         try:
@@ -354,6 +394,7 @@ class BamReader:
         t.seq = np.zeros(0, np.uint8)
         t.qual = np.zeros(0, np.uint8)
         t.aux = np.zeros(0, np.uint8)
+        t.known_masked = 0
         t._finish()
         return t
 

@@ -219,6 +219,8 @@ def hip_lib():
     lib.ganon_bam_dcols_download.argtypes = [_p, _p, C.POINTER(BamCols)]
     lib.ganon_bam_dcols_free.argtypes = [_p, _p]
     lib.ganon_ctx_set_name_key.argtypes = [_p, C.c_char_p, C.c_int32]
+    lib.ganon_ctx_set_known_sites.argtypes = [_p, C.c_int32, _i64p, _i32p, _u8p, C.c_int64, C.c_int32]
+    lib.ganon_ctx_known_sites_masked.argtypes = [_p, _i64p]
     lib.ganon_deflate_bound.argtypes = [C.c_int64, C.c_int32]
     lib.ganon_deflate_bound.restype = C.c_int64
     lib.ganon_deflate_bgzf.argtypes = [_p, _u8p, C.c_int64, C.c_int32, _u8p, C.c_int64, _i64p, _i32p]
@@ -258,7 +260,7 @@ EXPORTED_HIP_SYMBOLS = (
     "ganon_indel_upload", "ganon_indel_run", "ganon_indel_download", "ganon_indel_info", "ganon_indel_free",
     "ganon_inflate", "ganon_inflate_hostcb", "ganon_inflate_device_output",
     "ganon_bam_columns", "ganon_bam_dcols_get", "ganon_bam_dcols_download", "ganon_bam_dcols_free",
-    "ganon_ctx_set_name_key",
+    "ganon_ctx_set_name_key", "ganon_ctx_set_known_sites", "ganon_ctx_known_sites_masked",
     "ganon_pinned_alloc", "ganon_pinned_free", "ganon_pinned_stats", "ganon_region_decode",
     "ganon_deflate_bound", "ganon_deflate_bgzf",
 )
@@ -275,6 +277,8 @@ EXPORTED_HOST_SYMBOLS = (
     "ganon_objects_take_all", "ganon_aux_sa_count", "ganon_fastq_edit", "ganon_gather_ranges", "ganon_gather_ranges2", "ganon_host_phase_times",
     "ganon_bam_reader_set_inflater", "ganon_bam_reader_set_buffer_alloc", "ganon_bam_reader_set_region_decoder",
     "ganon_bam_open_keyed", "ganon_names_hash", "ganon_bam_reader_set_name_key",
+    "ganon_sites_create", "ganon_sites_destroy", "ganon_bam_open_ex", "ganon_bam_known_sites_masked",
+    "ganon_bam_reader_set_known_sites", "ganon_bam_reader_known_sites_masked",
 )
 
 
@@ -352,6 +356,7 @@ class GpuInflater:
         self.fn = C.cast(lib.ganon_inflate_hostcb, _p)   # the reader's callback, user = the context
         self.region_fn = C.cast(lib.ganon_region_decode, _p)   # the reader's region decoder, same user
         self.name_key: Optional[bytes] = None
+        self.known_sites = None
 
     @property
     def handle(self):
@@ -367,6 +372,33 @@ class GpuInflater:
         if self._lib.ganon_ctx_set_name_key(self._h, key, len(key)) != 0:
             raise GanonError(self._lib.ganon_last_error(self._h).decode(errors="replace"))
         self.name_key = key or None
+
+    def set_known_sites(self, table) -> None:
+        """--known_sites: the context's BAM decoder (``bam_columns``, the region decoder) applies the
+        panel mask of ``table`` (a known_sites.SitesTable) from now on: the table is uploaded to device
+        memory (``ganon_ctx_set_known_sites``) and stays there until it is replaced; None or a table
+        without sites clears it. Setting the table already in place does nothing."""
+        if table is not None and table.n == 0:
+            table = None
+        if table is self.known_sites:
+            return
+        if table is None:
+            rc = self._lib.ganon_ctx_set_known_sites(self._h, 0, None, None, None, 0, -1)
+        else:
+            rc = self._lib.ganon_ctx_set_known_sites(self._h, table.n_ref, _ptr(table.site_off, _i64p),
+                                                     _ptr(table.site_pos, _i32p), _ptr(table.site_code, _u8p),
+                                                     table.n, table.quality)
+        if rc != 0:
+            raise GanonError(self._lib.ganon_last_error(self._h).decode(errors="replace"))
+        self.known_sites = table
+
+    def known_sites_masked(self) -> int:
+        """Bases the context's decoder rewrote so far, over every table it held
+        (``ganon_ctx_known_sites_masked``)."""
+        c = C.c_int64(0)
+        if self._lib.ganon_ctx_known_sites_masked(self._h, C.byref(c)) != 0:
+            raise GanonError(self._lib.ganon_last_error(self._h).decode(errors="replace"))
+        return int(c.value)
 
     def kernel_ms(self) -> float:
         """k_inflate's time in the last profiled inflate (HIP events on the context's stream)."""
@@ -1760,6 +1792,15 @@ def host_lib():
     lib.ganon_bam_open_keyed.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int32, C.POINTER(_p)]
     lib.ganon_names_hash.argtypes = [C.c_void_p, _i64p, _i32p, C.c_int64, C.c_char_p, C.c_int32, C.c_int, C.c_void_p]
     lib.ganon_bam_reader_set_name_key.argtypes = [_p, C.c_char_p, C.c_int32]
+    lib.ganon_sites_create.argtypes = [C.c_int32, _i64p, _i32p, _u8p, C.c_int32, C.POINTER(_p)]
+    lib.ganon_sites_destroy.argtypes = [_p]
+    lib.ganon_sites_destroy.restype = None
+    lib.ganon_bam_open_ex.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int32, _p, C.POINTER(_p)]
+    lib.ganon_bam_known_sites_masked.argtypes = [_p]
+    lib.ganon_bam_known_sites_masked.restype = C.c_int64
+    lib.ganon_bam_reader_set_known_sites.argtypes = [_p, _p]
+    lib.ganon_bam_reader_known_sites_masked.argtypes = [_p]
+    lib.ganon_bam_reader_known_sites_masked.restype = C.c_int64
     lib.ganon_bam_view_get.argtypes = [_p, C.POINTER(BamView)]
     lib.ganon_bam_close.argtypes = [_p]
     lib.ganon_bam_reader_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(_p)]

@@ -68,8 +68,13 @@ def anonymize_genome(windows_in_sample: List[Window], tumor_bam_file: str, norma
         return timing
     t0 = time.time()
     name_key = native.read_name_key_default()   # --hash_read_names (None: off)
-    tumor = ReadTable(tumor_bam_file, threads=available_threads, name_key=name_key)
-    normal = ReadTable(normal_bam_file, threads=available_threads, name_key=name_key)
+    from .known_sites import pair_default
+    known = pair_default(fasta, windows_in_sample)   # --known_sites (None: off)
+    tumor = ReadTable(tumor_bam_file, threads=available_threads, name_key=name_key, known_sites=known)
+    normal = ReadTable(normal_bam_file, threads=available_threads, name_key=name_key, known_sites=known)
+    if known is not None:
+        log.info("known sites: %d bases rewritten by this process's decodes (tumor and normal)",
+                 tumor.known_masked + normal.known_masked)
     if has_split_alignments(tumor) or has_split_alignments(normal):
         log.info("secondary / supplementary alignments or SA tags: the sample streams contig by contig")
         del tumor, normal   # (the streamed path decodes job by job: do not hold the whole sample too)

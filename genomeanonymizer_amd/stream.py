@@ -1199,6 +1199,9 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
     compress = native.compress_output_default() if compress_output is None else bool(compress_output)
     # --hash_read_names: one key for every reader of the run, rank 0's on every rank (None: off)
     name_key = native.share_read_name_key(dist)
+    # --known_sites: the panel less this pair's own SNVs, loaded by every rank itself (None: off)
+    from .known_sites import pair_default
+    known = pair_default(fasta, windows)
     deflater = None
     spools: List[str] = []
     segs: List[Tuple[int, int, int, int]] = []   # (job, file, spool offset, compressed length) of this rank's jobs
@@ -1230,8 +1233,8 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
             if os.path.exists(p):
                 os.remove(p)
         raise
-    readers = (BamReader(tumor_bam, threads, window_bytes, name_key=name_key),
-               BamReader(normal_bam, threads, window_bytes, name_key=name_key))
+    readers = (BamReader(tumor_bam, threads, window_bytes, name_key=name_key, known_sites=known),
+               BamReader(normal_bam, threads, window_bytes, name_key=name_key, known_sites=known))
     # jobs: contigs, or runs of sections of about GANON_JOB_BP bases (default 4 Mb; 0 = whole
     # contigs) when both BAMs are indexed
     # (unset: 4 Mb, or smaller so that every rank gets about GANON_JOBS_PER_RANK jobs (default 3, at
@@ -1385,7 +1388,7 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
             job.forced = sorted(set(force) | set(job.forced))
             return job
         if not redo_readers:
-            redo_readers.extend(BamReader(p, threads, window_bytes, name_key=name_key)
+            redo_readers.extend(BamReader(p, threads, window_bytes, name_key=name_key, known_sites=known)
                                 for p in (tumor_bam, normal_bam))
         prep = JobPrep(job.spec, redo_readers, fasta, windows, secondaries=secondaries, force=force)
         done = Future()
@@ -1479,7 +1482,7 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
                         timing["spec_replans"] = timing.get("spec_replans", 0) + 1
                         job.release_device()
                         if not redo_readers:
-                            redo_readers.extend(BamReader(p, threads, window_bytes, name_key=name_key)
+                            redo_readers.extend(BamReader(p, threads, window_bytes, name_key=name_key, known_sites=known)
                                                 for p in (tumor_bam, normal_bam))
                         prep = JobPrep(job.spec, redo_readers, fasta, windows, secondaries=secondaries, force=full)
                         done = Future()
@@ -1607,6 +1610,12 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
                 os.remove(p)
             except OSError:
                 pass
+        if known is not None and failure is None:   # (before the readers close: host and device decodes)
+            timing["known_sites_masked"] = sum(r.known_masked() for r in list(readers) + list(redo_readers))
+            import logging
+            logging.getLogger("genomeanonymizer_amd").info(
+                "known sites: %d bases rewritten by this process's decodes (tumor and normal)",
+                timing["known_sites_masked"])
         # the readers' file mappings go on a thread of their own (unmapping a chromosome's BAM
         # took part of every rank's tail; nothing waits for it)
         threading.Thread(target=_close_all, args=(list(readers) + list(redo_readers),), daemon=True).start()

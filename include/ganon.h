@@ -452,6 +452,18 @@ GANON_API int ganon_bam_dcols_free(ganon_ctx *ctx, ganon_bam_dcols *c);
  * to the host to be hashed. key_len 0 clears the key: no kernel is added and the decoder's kernels
  * are those of a context that never had one. The key is kept in the context only. */
 GANON_API int ganon_ctx_set_name_key(ganon_ctx *ctx, const uint8_t *key, int32_t key_len);
+/* --known_sites (additive; the ABI version stays 5). ganon_ctx_set_known_sites uploads a panel table to
+ * device memory (the layout and the rule of include/ganon_host.h ganon_sites_create: n_ref sequences,
+ * site_off[n_ref + 1], n = site_off[n_ref] sites of site_pos / site_code, quality -1 or 0..93; checked
+ * here as there), where it stays until it is replaced or cleared (n = 0). With a table, ganon_bam_columns
+ * and ganon_region_decode on this context run k_bam_known_mask after the scatter, over the columns in
+ * device memory (in a region read: the kept records only), and return the bytes the host decoder
+ * returns with the same table. Without one no kernel is added and the decoder's kernels are those of a
+ * context that never had one. ganon_ctx_known_sites_masked: the bases rewritten on this context so far,
+ * over every table it held (it waits for the context's stream). */
+GANON_API int ganon_ctx_set_known_sites(ganon_ctx *ctx, int32_t n_ref, const int64_t *site_off, const int32_t *site_pos,
+                                        const uint8_t *site_code, int64_t n, int32_t quality);
+GANON_API int ganon_ctx_known_sites_masked(ganon_ctx *ctx, int64_t *masked);
 
 /* A region read's window decoded on the device: the reader's region decoder (ganon_region_fn of
  * include/ganon_host.h, user = a ganon_ctx; libganon_host.so's ganon_bam_reader_region, the

@@ -69,6 +69,27 @@ GANON_HOST_API int ganon_bam_open_keyed(const char *path, int threads, const uin
  * the 32 characters and a NUL. For tests and tools. */
 GANON_HOST_API int ganon_names_hash(const char *names, const int64_t *off, const int32_t *len, int64_t n,
                                     const uint8_t *key, int32_t key_len, int threads, char *out);
+/* --known_sites (additive). A panel of known single-nucleotide variants as a table by BAM reference
+ * sequence: sequence t owns the sites [site_off[t], site_off[t + 1]) of site_pos (0-based, strictly
+ * increasing inside a sequence) and site_code = ref_nt16 << 4 | alt_mask (nt16 is a bit set: A 1, C 2,
+ * G 4, T 8; ref_nt16 one of them, alt_mask the OR of the ALT alleles and never the reference's bit).
+ * A decoder with such a table rewrites, where a record is decoded, every base that is aligned (CIGAR
+ * M, = or X; query index < l_seq) to a listed position, is one of A, C, G, T and is in the site's
+ * alt_mask: its nibble becomes ref_nt16, and with quality >= 0 (0..93; -1: qualities stay) its quality
+ * byte becomes `quality` unless the record's first quality byte is 0xFF. Records with flag & 4,
+ * tid < 0, no CIGAR or no bases are left alone, as is every other column and blob. The arrays are
+ * copied; ganon_sites_create checks them. The handle may be destroyed while tables or readers made
+ * with it live on. No process-global state. */
+typedef struct ganon_sites ganon_sites;
+GANON_HOST_API int ganon_sites_create(int32_t n_ref, const int64_t *site_off, const int32_t *site_pos,
+                                      const uint8_t *site_code, int32_t quality, ganon_sites **out);
+GANON_HOST_API void ganon_sites_destroy(ganon_sites *sites);
+/* ganon_bam_open with a read-name key (key_len 0: none) and / or a known-sites table (NULL: none). */
+GANON_HOST_API int ganon_bam_open_ex(const char *path, int threads, const uint8_t *key, int32_t key_len,
+                                     const ganon_sites *sites, ganon_bam **out);
+/* The bases the panel mask rewrote while this table was decoded on the host (0 for a table a region
+ * decoder made: include/ganon.h ganon_ctx_known_sites_masked counts those). */
+GANON_HOST_API int64_t ganon_bam_known_sites_masked(const ganon_bam *bam);
 GANON_HOST_API int ganon_bam_view_get(ganon_bam *bam, ganon_bam_view *view);
 GANON_HOST_API const char *ganon_bam_error(ganon_bam *bam);
 GANON_HOST_API void ganon_bam_close(ganon_bam *bam);
@@ -128,6 +149,12 @@ GANON_HOST_API int ganon_bam_reader_set_region_decoder(ganon_bam_reader *reader,
  * past it. A region decoder must hash with the same key (ganon_ctx_set_name_key on its context).
  * key_len 0 turns it off. */
 GANON_HOST_API int ganon_bam_reader_set_name_key(ganon_bam_reader *reader, const uint8_t *key, int32_t key_len);
+/* --known_sites: the tables of ganon_bam_reader_contig and ganon_bam_reader_region are masked by the
+ * panel from now on, inside the column pass on the reader's threads — the host path of a region read
+ * too. A region decoder must hold the same table (ganon_ctx_set_known_sites on its context). NULL
+ * turns it off. ganon_bam_reader_known_sites_masked: the bases this reader's host decodes rewrote. */
+GANON_HOST_API int ganon_bam_reader_set_known_sites(ganon_bam_reader *reader, const ganon_sites *sites);
+GANON_HOST_API int64_t ganon_bam_reader_known_sites_masked(const ganon_bam_reader *reader);
 GANON_HOST_API int ganon_bam_reader_header(ganon_bam_reader *reader, ganon_bam_view *view);
 GANON_HOST_API int ganon_bam_reader_contig(ganon_bam_reader *reader, int32_t tid, ganon_bam **out);
 /* The records of tid overlapping [beg, end) (0-based; htslib's region semantics: pos < end and

@@ -12,6 +12,11 @@ JSON line (bench.py's `bam_decode` side line runs this as a child).
 --hash_names: the same with a read-name key on both sides (--hash_read_names: GANON_READ_NAME_KEY as
 hex, else a fixed benchmark key): k_bam_name_hash joins the kernel list, the names block is 33 bytes a
 record, and the host decoder hashes inside its column pass.
+
+--known_sites SITES_PER_KB: the same with a synthetic panel on both sides (--known_sites: that many random
+positions per 1,000 bases of each sequence, REF the FASTA's base, one random ALT): k_bam_known_mask joins
+the kernel list, the host decoder masks inside its column pass, and the line reports the sites and the
+bases rewritten.
 """
 import argparse
 import json
@@ -34,7 +39,30 @@ HBM_PEAK_GBPS = 8000.0
 BENCH_KEY = bytes(range(32))
 
 
-def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = None) -> dict:
+def synthetic_panel(ref_path: str, ref_names, per_kb: float, seed: int = 1):
+    """A known_sites.SitesTable of about ``per_kb`` sites per 1,000 bases of each BAM sequence."""
+    from genomeanonymizer_amd.io.fasta import FastaRef
+    from genomeanonymizer_amd.known_sites import SitesTable
+    fa = FastaRef(ref_path)
+    rng = np.random.default_rng(seed)
+    lut = np.zeros(256, np.uint8)
+    for c, v in zip(b"ACGTacgt", (1, 2, 4, 8) * 2):
+        lut[c] = v
+    off, pos, code = [0], [], []
+    for name in ref_names:
+        seq = np.frombuffer(fa.raw(name), np.uint8)
+        p = np.unique(rng.integers(0, len(seq), int(len(seq) * per_kb / 1000)))
+        ref = lut[seq[p]]
+        p, ref = p[ref != 0], ref[ref != 0]
+        alt = np.uint8(1) << rng.integers(0, 4, len(p)).astype(np.uint8)
+        alt = np.where(alt == ref, np.where(ref == 8, 1, ref << 1), alt).astype(np.uint8)
+        pos.append(p.astype(np.int32))
+        code.append(((ref << 4) | alt).astype(np.uint8))
+        off.append(off[-1] + len(p))
+    return SitesTable(np.array(off, np.int64), np.concatenate(pos), np.concatenate(code))
+
+
+def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = None, sites_per_kb: float = 0.0) -> dict:
     import gzip
     from genomeanonymizer_amd import native
     from genomeanonymizer_amd.io.bam import ReadTable
@@ -52,6 +80,13 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
         lib = native.hip_lib()
         g.set_profiling(True)
         g.set_name_key(name_key)
+        table = None
+        if sites_per_kb > 0:
+            from genomeanonymizer_amd.io.bam import BamReader
+            hdr = BamReader(paths["T"], 1)
+            table = synthetic_panel(paths["ref"], hdr.ref_names, sites_per_kb)
+            hdr.close()
+        g.set_known_sites(table)
         runs = []
         cols, _ = native.bam_columns_device(g.handle, stream, p, len(stream), on_host=True)   # (warm: blocks cached)
         for _ in range(reps):
@@ -65,6 +100,7 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
                 name = arr[i].name.decode()
                 per[name] = per.get(name, 0.0) + float(arr[i].ms)
             runs.append((sum(per.values()), per, wall, fixes))
+        dev_masked = g.known_sites_masked() // (reps + 1) if table is not None else 0
         g.close()
         best = min(runs, key=lambda x: x[0])
         nr = len(cols["pos"])
@@ -74,7 +110,7 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
         t = None
         for th in (1, threads):
             t0 = time.perf_counter()
-            t = ReadTable(path, threads=th, name_key=name_key)
+            t = ReadTable(path, threads=th, name_key=name_key, known_sites=table)
             host[th] = time.perf_counter() - t0
         equal = len(cols["pos"]) == t.n and all(np.array_equal(cols[f], getattr(t, f)) for f in COLS + BLOBS)
         out_bytes = sum(cols[f].nbytes for f in COLS + BLOBS) + cols["rec_off"].nbytes
@@ -91,6 +127,9 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
             "host_decoder_s": {str(k): round(v, 3) for k, v in host.items()},
             "host_records_per_s": {str(k): round(nr / v, 1) for k, v in host.items()},
             "columns_equal_host_decoder": bool(equal), "hashed_names": name_key is not None,
+            "known_sites": None if table is None else {
+                "sites_per_kb": sites_per_kb, "sites": table.n, "table_bytes": int(5 * table.n + 8 * (table.n_ref + 1)),
+                "bases_rewritten_device": int(dev_masked), "bases_rewritten_host": int(t.known_masked)},
             "workload": f"configs[0] tumor BAM records tiled x{tiles} ({nr} records, 150 bp); device: the stream "
                         f"resident in HBM, kernels only (HIP events on the context's stream); call wall adds the H2D "
                         f"copy, the scans' host reads and the D2H of the columns; host: ganon_bam_open of the same "
@@ -107,13 +146,15 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--hash_names", action="store_true",
                     help="decode with a read-name key (GANON_READ_NAME_KEY as hex, else a fixed benchmark key)")
+    ap.add_argument("--known_sites", type=float, default=0.0, metavar="SITES_PER_KB",
+                    help="decode with a synthetic panel of this many sites per 1,000 bases (both sides)")
     args = ap.parse_args()
     key = None
     if args.hash_names:
         from genomeanonymizer_amd import native
         v = os.environ.get(native.NAME_KEY_ENV)
         key = native.parse_name_key(v) if v is not None else BENCH_KEY
-    print(json.dumps(measure(args.mb, args.threads, args.reps, key)))
+    print(json.dumps(measure(args.mb, args.threads, args.reps, key, args.known_sites)))
 
 
 if __name__ == "__main__":

@@ -23,6 +23,8 @@ Prints one JSON line with per-stage seconds, reads/s, bases/s and the process's 
                              # same line with "masked_base_quality": Q
     GANON_HASH_READ_NAMES=1 GANON_READ_NAME_KEY=HEX  # --hash_read_names: read names hashed at decode (DESIGN
                              # §4h): the same line with "hash_read_names": true
+    GANON_KNOWN_SITES=PANEL.vcf[.gz]  # --known_sites: panel SNVs masked at decode: the same line
+                             # with "known_sites": the path
     E2E_DISK_PROBE=1 ...     # also time 2 GiB of pwrite into OUTDIR (4 files at once, as the product
                              # writes; page cache, then with fsync): the box's write bandwidth
 """
@@ -217,6 +219,7 @@ def main():
                      "compress_output": bool(gz),
                      "masked_base_quality": _native.masked_base_quality_default(),
                      "hash_read_names": _native.read_name_key_default() is not None,
+                     "known_sites": os.environ.get("GANON_KNOWN_SITES") or None,
                      "cpus_available": len(os.sched_getaffinity(0)),
                      "output_bytes": sum(os.path.getsize(os.path.join(out, f"{x}_{mode}{s}{gz}"))
                                          for x in ("tumor", "normal") for s in (".1.fastq", ".2.fastq"))}

@@ -19,8 +19,9 @@
 //               unit's source dwords loaded in one round (3 units per lane), transformed (names
 //               as they are, qualities + 33 per byte, bases as nibbles through two v_perm table
 //               lookups, reverse complement with a zero-byte test for the Q7 error) and written.
-//   k_fq_quad / k_fq_rows / k_fq_format: earlier designs kept as A/B instances
-//               (GANON_PARAM_FASTQ_KD); k_fq_dense takes tiles with more than 64 records.
+//   k_fq_quad / k_fq_rows: earlier designs kept as A/B instances (GANON_PARAM_FASTQ_KD), as are
+//               four more k_fq_span instantiations; the round-1 dword kernel is retired (DESIGN
+//               §4c). k_fq_dense takes tiles with more than 64 records.
 //   k_fq_maskq  (--masked_base_quality only, after ganon_fastq_set_maskq) a post-pass over the
 //               formatted text: the quality under every base an SNV mask wrote becomes '!' + Q.
 #include "ganon_ctx.h"
@@ -164,72 +165,6 @@ __device__ __forceinline__ const uint8_t *pick4(const uint8_t *const (&p)[kFqMax
   return (sel & 2) ? b : a;
 }
 
-// Per output byte (record offset o of record R): its source and how it is transformed.
-// info = constant value | kind << 8 (0 const, 1 raw name byte, 2 nt16 nibble, 3 quality) |
-//        low nibble << 10 | reverse << 11
-struct FqSrc {
-  const uint8_t *addr;
-  uint32_t info;
-};
-
-__device__ __forceinline__ FqSrc fq_src(const FqRec &R, uint32_t o, const FqBufs &bufs) {
-  const uint32_t NL = (uint32_t)(R.name >> 48), L = R.len, Q = R.qlen;
-  FqSrc s{bufs.names, 0u};
-  if (o == 0) {
-    s.info = '@';
-    return s;
-  }
-  o -= 1;
-  if (o < NL) {
-    s.addr = bufs.names + (R.name & kOff48) + o;
-    s.info = 1u << 8;
-    return s;
-  }
-  o -= NL;
-  if (o < 3) {
-    s.info = o == 0 ? '/' : o == 1 ? (((uint32_t)(R.qual >> 48) & 0xFF) + '0') & 0xFF : '\n';
-    return s;
-  }
-  o -= 3;
-  if (o < L) {
-    const uint32_t rev = (uint32_t)(R.seq >> 58) & 1;
-    const uint64_t nib = (R.seq & kOff56) + (rev ? L - 1 - o : o);
-    s.addr = pick4(bufs.seq, (uint32_t)(R.seq >> 56) & 3) + (nib >> 1);
-    s.info = (2u << 8) | ((uint32_t)(nib & 1) << 10) | (rev << 11);
-    return s;
-  }
-  o -= L;
-  if (o < 3) {
-    s.info = o == 1 ? '+' : '\n';
-    return s;
-  }
-  o -= 3;
-  if (o < Q) {
-    const uint32_t qrev = (uint32_t)(R.seq >> 59) & 1;
-    s.addr = pick4(bufs.qual, (uint32_t)(R.qual >> 56) & 3) + (R.qual & kOff48) + (qrev ? Q - 1 - o : o);
-    s.info = 3u << 8;
-    return s;
-  }
-  s.info = '\n';
-  return s;
-}
-
-__device__ __forceinline__ uint32_t fq_val(uint32_t info, uint32_t byte, bool &bad) {
-  const uint32_t kind = (info >> 8) & 3;
-  if (kind == 1) return byte;
-  if (kind == 3) return (byte + 33) & 0xFF;
-  if (kind == 2) {
-    const uint32_t c = (info >> 10) & 1 ? (byte & 0xF) : (byte >> 4);
-    if ((info >> 11) & 1) {
-      const uint32_t x = tab16(kRevLo, kRevHi, c);
-      bad |= x == 0;
-      return x;
-    }
-    return tab16(kFwdLo, kFwdHi, c);
-  }
-  return info & 0xFF;
-}
-
 // nt16 codes (one per byte of c, 0..15) -> table bytes, two v_perm over the 16-byte table.
 __device__ __forceinline__ uint32_t nt16_lut(uint32_t c, uint64_t lo, uint64_t hi) {
   const uint32_t sel = c & 0x07070707u;
@@ -270,8 +205,7 @@ __device__ __forceinline__ int fq_edge(const FqField &F, int e) {
   return F.ib + (e - 3) < F.b ? F.ib + (e - 3) : -1;
 }
 
-// One record into the tile image by one wave, in three phases so that a wave can keep the
-// loads of several records in flight (k_fq_format batches NB records): prep computes every
+// One record into the tile image by one wave, in three phases: prep computes every
 // source address, load issues the loads, finish transforms and writes. Every branch is
 // wave-uniform except the lane-range guards: name / base / quality interiors as aligned dwords
 // (two dword loads, a v_perm or SWAR transform, ds_write_b32), the <= 6 edge bytes of each
@@ -446,11 +380,7 @@ struct FqSpan {
   uint32_t flags;  // reverse | f << 1
 };
 static_assert(sizeof(FqSpan) == 24, "FqSpan layout");
-constexpr int kFqDw = kFqTile / 4;   // dwords per tile
-constexpr int kFqMap = 4096;         // virtual dwords: tile dwords + up to 3 shared edge dwords per record
-static_assert(kFqMap >= kFqDw + 3 * kFqStage, "virtual dword map");
 constexpr size_t kFqSmemA = kFqTile + kFqStage * sizeof(FqRec) + (kFqStage + 1) * sizeof(uint64_t);
-constexpr size_t kFqSmemB = kFqTile + kFqMap * sizeof(uint16_t) + 3 * kFqStage * sizeof(FqSpan);
 
 // Block-wide exclusive scan of a u64 (packed counters), 256 threads; returns the total too.
 __device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long v, unsigned long long *s_w,
@@ -472,232 +402,15 @@ __device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long
   return pre;
 }
 
-template <int KD>
-__global__ void __launch_bounds__(kFqThreads) k_fq_format(const FqBufs bufs, const FqRec *__restrict__ recs,
-                                                          const uint64_t *__restrict__ off,
-                                                          const int64_t *__restrict__ tile_first, int64_t n,
-                                                          uint64_t total, uint8_t *__restrict__ out,
-                                                          unsigned long long *__restrict__ err, int skip,
-                                                          int *__restrict__ dense_list,
-                                                          unsigned int *__restrict__ dense_count) {
-  __shared__ __attribute__((aligned(16))) uint8_t smem[kFqSmemB];
-  __shared__ unsigned long long s_w[kFqThreads / 64];
-  const uint64_t t0 = (uint64_t)blockIdx.x * kFqTile;
-  const int64_t r0 = tile_first[blockIdx.x];
-  const int64_t rl = (t0 + kFqTile < total) ? tile_first[blockIdx.x + 1] : n - 1;   // last record touching the tile
-  const int t = threadIdx.x;
-  unsigned long long bad = ~0ull;
-  uint8_t *tile = smem;
-  uint32_t *tile32 = reinterpret_cast<uint32_t *>(smem);
-  if (rl - r0 + 1 > kFqStage) {   // left to k_fq_dense
-    if (t == 0) dense_list[atomicAdd(dense_count, 1u)] = (int)blockIdx.x;
-    return;
-  }
-  {
-    const int ns = (int)(rl - r0 + 1);
-    uint16_t *map = reinterpret_cast<uint16_t *>(smem + kFqTile);   // virtual dword -> span
-    FqSpan *spans = reinterpret_cast<FqSpan *>(smem + kFqTile + kFqMap * sizeof(uint16_t));
-    // 1. zero tile and map; one thread per record: its three field spans (the tile dwords each
-    //    field touches — neighbouring fields share edge dwords, OR-ed together) and, once the
-    //    tile is zero, its 8 constant bytes
-    reinterpret_cast<uint4 *>(tile)[t] = make_uint4(0, 0, 0, 0);
-    reinterpret_cast<uint4 *>(tile)[t + kFqThreads] = make_uint4(0, 0, 0, 0);
-    reinterpret_cast<uint4 *>(map)[t] = make_uint4(0, 0, 0, 0);
-    reinterpret_cast<uint4 *>(map)[t + kFqThreads] = make_uint4(0, 0, 0, 0);
-    unsigned long long cnt = 0;   // dwords touched: bases | qualities << 16 | name << 32
-    FqSpan sp[3];
-    int64_t P0 = 0;
-    uint32_t NL = 0, L = 0, Q = 0, mate = 0;
-    if (t < ns) {
-      const FqRec R = recs[r0 + t];
-      P0 = (int64_t)off[r0 + t] - (int64_t)t0;
-      NL = (uint32_t)(R.name >> 48);
-      L = R.len;
-      Q = R.qlen;
-      mate = (uint32_t)((R.qual >> 48) & 0xFF);
-      const uint32_t fa[3] = {NL + 4, NL + 7 + L, 1u}, len[3] = {L, Q, NL};
-      const uint32_t rev[3] = {(uint32_t)(R.seq >> 58) & 1, (uint32_t)(R.seq >> 59) & 1, 0u};
-      const uint64_t src[3] = {2 * (uint64_t)(uintptr_t)pick4(bufs.seq, (uint32_t)(R.seq >> 56) & 3) + (R.seq & kOff56),
-                               (uint64_t)(uintptr_t)(pick4(bufs.qual, (uint32_t)(R.qual >> 56) & 3) + (R.qual & kOff48)),
-                               (uint64_t)(uintptr_t)(bufs.names + (R.name & kOff48))};
-#pragma unroll
-      for (int f = 0; f < 3; ++f) {
-        const FqField F = fq_field(P0, fa[f], len[f]);
-        const int d0 = F.a >> 2, d1 = (F.b + 3) >> 2;
-        sp[f].src = src[f];
-        sp[f].j0 = (int)(4 * (int64_t)d0 - (P0 + fa[f]));
-        sp[f].len = len[f];
-        sp[f].td0 = (uint16_t)d0;
-        sp[f].flags = rev[f] | (f << 1);
-        cnt |= (unsigned long long)(F.b > F.a ? d1 - d0 : 0) << (16 * f);
-      }
-    }
-    unsigned long long tot;
-    const unsigned long long pre = block_excl_scan(cnt, s_w, tot);   // (its barrier: tile and map are zero)
-    if (skip & 8) return;
-    const int V0 = (int)(tot & 0xFFFF), V1 = V0 + (int)((tot >> 16) & 0xFFFF), V = V1 + (int)((tot >> 32) & 0xFFFF);
-    if (t < ns) {
-      const int base[3] = {0, V0, V1};
-#pragma unroll
-      for (int f = 0; f < 3; ++f) {
-        const int c = (int)((cnt >> (16 * f)) & 0xFFFF);
-        const int v = base[f] + (int)((pre >> (16 * f)) & 0xFFFF);
-        sp[f].vs = (uint16_t)v;
-        spans[f * kFqStage + t] = sp[f];
-        if (c > 0) map[v] = (uint16_t)(f * kFqStage + t);
-      }
-      if (!(skip & 64)) {
-        const int64_t o[8] = {0, NL + 1, NL + 2, NL + 3, NL + 4 + L, NL + 5 + L, NL + 6 + L, NL + 7 + L + Q};
-        const uint32_t x[8] = {'@', '/', (mate + '0') & 0xFF, '\n', '\n', '+', '\n', '\n'};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int64_t p = P0 + o[e];
-          if (p >= 0 && p < kFqTile) atomicOr(&tile32[p >> 2], x[e] << (8 * (p & 3)));
-        }
-      }
-    }
-    __syncthreads();
-    // 2. fill forward (prefix max over f << 8 | record, increasing along the virtual dwords):
-    //    thread t owns map[16t, 16t + 16)
-    {
-      static_assert(kFqMap == 16 * kFqThreads, "two uint4 of the map per thread");
-      uint4 *m4 = reinterpret_cast<uint4 *>(map) + 2 * t;
-      const uint4 a = m4[0], b = m4[1];
-      uint32_t v[16] = {a.x & 0xFFFF, a.x >> 16, a.y & 0xFFFF, a.y >> 16, a.z & 0xFFFF, a.z >> 16, a.w & 0xFFFF, a.w >> 16,
-                        b.x & 0xFFFF, b.x >> 16, b.y & 0xFFFF, b.y >> 16, b.z & 0xFFFF, b.z >> 16, b.w & 0xFFFF, b.w >> 16};
-      uint32_t mx = 0;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mx = max(mx, v[i]);
-      uint32_t inc = mx;
-      const int lane = t & 63;
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o);
-        if (lane >= o) inc = max(inc, u);
-      }
-      __syncthreads();   // s_w reused
-      if (lane == 63) s_w[t >> 6] = inc;
-      __syncthreads();
-      uint32_t pm = __shfl_up(inc, 1);
-      if (lane == 0) pm = 0;
-      for (int w = 0; w < (t >> 6); ++w) pm = max(pm, (uint32_t)s_w[w]);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        pm = max(pm, v[i]);
-        v[i] = pm;
-      }
-      m4[0] = make_uint4(v[0] | v[1] << 16, v[2] | v[3] << 16, v[4] | v[5] << 16, v[6] | v[7] << 16);
-      m4[1] = make_uint4(v[8] | v[9] << 16, v[10] | v[11] << 16, v[12] | v[13] << 16, v[14] | v[15] << 16);
-    }
-    __syncthreads();
-    if (skip & 16) return;
-    // 3. field dwords: virtual dwords on consecutive lanes (one field type per wave but at the
-    //    two type changes), KD per lane at a time. The 4-byte source window is clamped inside the
-    //    field (never before a buffer's start), shifted into place and masked to the field's
-    //    bytes; whole dwords are written, edge dwords OR-ed into the zeroed tile.
-#pragma unroll 1
-    for (int vb = 0; vb < ((skip & 32) ? 0 : V); vb += kFqThreads * KD) {
-      uint32_t key[KD], sh[KD], par[KD], v0[KD], v1[KD], flg[KD];
-      int td_[KD], dsh[KD];   // dsh: byte shift from the clamped window to the wanted one
-      uint32_t msk[KD];
-      const uint32_t *a0[KD];
-#pragma unroll
-      for (int j = 0; j < KD; ++j) {
-        const int v = vb + j * kFqThreads + t;
-        key[j] = 0xFFFFu;
-        a0[j] = reinterpret_cast<const uint32_t *>(bufs.names);
-        sh[j] = par[j] = 0;
-        td_[j] = 0;
-        dsh[j] = 0;
-        msk[j] = 0;
-        flg[j] = 0;
-        if (v >= V) continue;
-        const uint32_t kf = map[v];
-        key[j] = kf;
-        const FqSpan S = spans[kf];
-        const int i = v - S.vs;
-        td_[j] = S.td0 + i;
-        const int j0 = S.j0 + 4 * i;   // field index of the dword's byte 0
-        const int len = (int)S.len;
-        // bytes i with 0 <= j0 + i < len
-        const int lo = max(0, -j0), hi = min(4, len - j0);
-        msk[j] = hi > lo ? (0xFFFFFFFFu >> (8 * (4 - (hi - lo)))) << (8 * lo) : 0u;
-        const bool rev = S.flags & 1;
-        // wanted source window start m (ascending source order), clamped into [0, max(0, len - 4)]
-        const int m = rev ? len - 4 - j0 : j0;
-        const int c = min(max(m, 0), max(0, len - 4));
-        dsh[j] = rev ? c - m : m - c;   // > 0: shift right, < 0: shift left (bytes)
-        const uint8_t *src;
-        if ((S.flags >> 1) == 0) {
-          const uint64_t nb = S.src + (uint64_t)c;
-          src = reinterpret_cast<const uint8_t *>(nb >> 1);
-          par[j] = (uint32_t)(nb & 1);
-        } else {
-          src = reinterpret_cast<const uint8_t *>(S.src + (uint64_t)c);
-        }
-        flg[j] = S.flags;
-        sh[j] = (uint32_t)((uintptr_t)src & 3);
-        a0[j] = reinterpret_cast<const uint32_t *>((uintptr_t)src & ~(uintptr_t)3);
-      }
-      if (!(skip & 1)) {
-#pragma unroll
-        for (int j = 0; j < KD; ++j) {
-          v0[j] = __builtin_nontemporal_load(a0[j]);
-          v1[j] = __builtin_nontemporal_load(a0[j] + 1);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < KD; ++j) v0[j] = v1[j] = 0x11111111u;
-      }
-#pragma unroll
-      for (int j = 0; j < KD; ++j) {
-        if (key[j] == 0xFFFFu || msk[j] == 0) continue;
-        const int f = flg[j] >> 1, k = key[j] % kFqStage;
-        const bool rev = flg[j] & 1;
-        const uint32_t w = __builtin_amdgcn_alignbyte(v1[j], v0[j], sh[j]);
-        const int ds = dsh[j];
-        auto place = [&](uint32_t y) {   // clamped window -> wanted window
-          return ds >= 0 ? y >> (8 * ds) : y << (8 * -ds);
-        };
-        uint32_t x;
-        if (f == 0) {
-          const uint32_t hiN = (w >> 4) & 0x0F0F0F0Fu, loN = w & 0x0F0F0F0Fu;
-          // codes in output order: forward [H0 L0 H1 L1] / [L0 H1 L1 H2], reverse the mirror
-          const uint32_t sel = rev ? (par[j] ? 0x04010502u : 0x00040105u) : (par[j] ? 0x02050104u : 0x05010400u);
-          const uint32_t cc = place(__builtin_amdgcn_perm(loN, hiN, sel));
-          x = rev ? nt16_lut(cc, kRevLo, kRevHi) : nt16_lut(cc, kFwdLo, kFwdHi);
-          const uint32_t y = x | ~msk[j];
-          if (rev && ((y - 0x01010101u) & ~y & 0x80808080u)) bad = min(bad, (unsigned long long)(r0 + k));
-        } else if (f == 1) {
-          x = add33(place(rev ? __builtin_bswap32(w) : w));
-        } else {
-          x = place(w);
-        }
-        if (msk[j] == 0xFFFFFFFFu) tile32[td_[j]] = x;
-        else atomicOr(&tile32[td_[j]], x & msk[j]);
-      }
-    }
-  }
-  if (bad != ~0ull && !(skip & 1)) atomicMin(err, bad);
-  __syncthreads();
-  if (skip & 2) return;
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-  for (int q = 0; q < kFqTile / (16 * kFqThreads); ++q) {
-    const int p = (q * kFqThreads + t) * 16;
-    if (t0 + p >= total) break;
-    __builtin_nontemporal_store(*reinterpret_cast<const u32x4 *>(tile + p), reinterpret_cast<u32x4 *>(out + t0 + p));
-  }
-}
-
-// ---- quad variant (GANON_PARAM_FASTQ_KD 16 / 9 / 10; the default up to round 4) --------------------
+// ---- quad variant (GANON_PARAM_FASTQ_KD 16 / 9 / 11; the default up to round 4) -------------------
 // The same tile design with 16-byte units: a virtual unit is one 16-byte-aligned tile quad of one
 // field, so the map / span lookup and the address arithmetic are paid once per 16 output bytes
-// instead of once per 4 (the dword kernel above is VALU-bound: without loads and stores it still
-// takes 2.2 of its 2.6 ms on configs[1]'s 10 M records). Each unit loads the aligned dwords under its
+// instead of once per 4 (the retired round-1 dword kernel was VALU-bound: without loads and stores it
+// still took 2.2 of its 2.6 ms on configs[1]'s 10 M records). Each unit loads the aligned dwords under its
 // 16-byte source window (3 for bases: 16 nibbles; 5 for names / qualities), every dword address
 // clamped into the field's own aligned extent (bytes outside the field are masked off anyway, so a
 // clamped dword never matters and no load leaves the field's allocation), builds the four output
-// dwords with the dword kernel's transforms and writes them with one ds_write_b128 when the quad
+// dwords with fq_finish's per-dword transforms and writes them with one ds_write_b128 when the quad
 // lies inside the field, else per dword (whole dwords stored, edge dwords OR-ed). The virtual map is
 // 4x smaller, so the fill-forward scan is too.
 constexpr int kFqQMap = 1024;        // virtual quads: 512 tile quads + up to 3 shared per record
@@ -707,10 +420,6 @@ constexpr size_t kFqSmemQ = kFqTile + kFqQMap * sizeof(uint16_t) + 3 * kFqStage 
 __device__ __forceinline__ uint32_t fq_dmask(int jd, int len) {   // bytes of dword jd..jd+3 inside [0, len)
   const int lo = max(0, -jd), hi = min(4, len - jd);
   return hi > lo ? (0xFFFFFFFFu >> (8 * (4 - (hi - lo)))) << (8 * lo) : 0u;
-}
-
-__device__ __forceinline__ const uint32_t *fq_clamp(uintptr_t a, uintptr_t lo, uintptr_t hi) {
-  return reinterpret_cast<const uint32_t *>(a < lo ? lo : a > hi ? hi : a);
 }
 
 typedef __attribute__((address_space(1))) const uint32_t GU32;
@@ -1467,7 +1176,7 @@ __global__ void __launch_bounds__(kFqThreads) k_fq_rows(const FqBufs bufs, const
 }
 
 // Tiles touched by more than kFqStage records (records of a few dozen bytes), listed by
-// k_fq_format: built in LDS record by record (one wave per record), a fixed grid looping over
+// the tile kernel: built in LDS record by record (one wave per record), a fixed grid looping over
 // the list.
 __global__ void __launch_bounds__(kFqThreads) k_fq_dense(const FqBufs bufs, const FqRec *__restrict__ recs,
                                                          const uint64_t *__restrict__ off,
@@ -1608,10 +1317,6 @@ __device__ __forceinline__ void mq_record(const FqBufs &bufs, const MqBufs &ob, 
     mq_issue(c, bufs, ob, R, o, first, true, safe);
     mq_store(mq_finish(c, R, first), R, first, q, qc);
   }
-}
-
-__device__ __forceinline__ bool mq_wanted(const FqRec &R, uint64_t o) {
-  return o != ~0ull && R.len != 0 && R.qlen == R.len;
 }
 
 __device__ __forceinline__ uint8_t *mq_qual(uint8_t *out, uint64_t off, const FqRec &R) {
@@ -1863,13 +1568,8 @@ GANON_API int ganon_fastq_run(ganon_ctx *ctx, ganon_fastq *f) {
   }
   {
     KernelScope ks(ctx, "k_fq_format");
-    // virtual dwords per lane per round: a tile holds ~2,100 of them (2,048 tile dwords plus the
-    // dwords neighbouring fields share), so the width sets the number of dependent load rounds
-    const int kd = ctx->fq_kd;
-    auto kern = kd == 16 ? k_fq_quad<2> : kd == 12 ? k_fq_rows : kd == 9 ? k_fq_quad<1> : kd == 10 ? k_fq_quad<3>
-              : kd == 11 ? k_fq_quad<2, false>
-              : kd == 1 ? k_fq_format<1> : kd == 2 ? k_fq_format<2> : kd == 3 ? k_fq_format<3>
-              : kd == 5 ? k_fq_format<5> : kd == 6 ? k_fq_format<6> : kd == 8 ? k_fq_format<8> : k_fq_format<4>;
+    const int kd = ctx->fq_kd;   // validated by ganon_ctx_set_param: 0, 9, 11-17
+    auto kern = kd == 12 ? k_fq_rows : kd == 9 ? k_fq_quad<1> : kd == 11 ? k_fq_quad<2, false> : k_fq_quad<2>;
     if (kd == 0 || (kd >= 13 && kd <= 15) || kd == 17) {   // span kernels (default: 3 units per lane, one 8 KiB tile)
       const int tm = kd == 14 ? 2 : 1;
       auto sk = kd == 0 ? k_fq_span<3, 1, true> : kd == 13 ? k_fq_span<2, 1> : kd == 14 ? k_fq_span<2, 2>

@@ -617,7 +617,7 @@ GANON_API int ganon_ctx_set_param(ganon_ctx *ctx, int param, int value) {
     return GANON_OK;
   }
   if (param == GANON_PARAM_FASTQ_SKIP) {
-    ctx->fq_skip = value & 127;
+    ctx->fq_skip = value & 0x3B;   // k_fq_span and k_fq_quad read bits 0, 1, 3, 4, 5; k_fq_rows 1 and 5; k_fq_dense none
     return GANON_OK;
   }
   if (param == GANON_PARAM_INDEL_SORT) {
@@ -626,12 +626,14 @@ GANON_API int ganon_ctx_set_param(ganon_ctx *ctx, int param, int value) {
     return GANON_OK;
   }
   if (param == GANON_PARAM_FASTQ_KD) {
+    if ((value >= 1 && value <= 6) || value == 8 || value == 10)
+      return fail(ctx, GANON_E_ARG, "FASTQ kernel instance %d was retired (the round-1 dword kernel, 3 quads per lane)",
+                  value);
     if (value < 0 || value > 17 || value == 7)
       return fail(ctx, GANON_E_ARG,
                   "FASTQ kernel: 0 (spans, 3 units per lane), 13 / 14 (spans, 2 per lane, 8 / 16 KiB tiles), "
                   "15 / 17 (as 0, span found by binary search / from a map entry per 8 units), "
-                  "16 / 9 / 10 (quads, 2 / 1 / 3 per lane), 11 (quads, per-dword base select), "
-                  "12 (record rows), dwords per lane 1-6 or 8");
+                  "16 / 9 (quads, 2 / 1 per lane), 11 (quads, per-dword base select), 12 (record rows)");
     ctx->fq_kd = value;
     return GANON_OK;
   }

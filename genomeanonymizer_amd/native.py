@@ -236,7 +236,7 @@ PARAM_GROUP_TARGET = 3   # include/ganon.h GANON_PARAM_GROUP_TARGET (cost units 
 PARAM_NT_COPY = 4        # include/ganon.h GANON_PARAM_NT_COPY
 PARAM_REF2 = 5           # include/ganon.h GANON_PARAM_REF2
 PARAM_FASTQ_SKIP = 6     # include/ganon.h GANON_PARAM_FASTQ_SKIP (phase timing only)
-PARAM_FASTQ_KD = 7       # include/ganon.h GANON_PARAM_FASTQ_KD
+PARAM_FASTQ_KD = 7       # include/ganon.h GANON_PARAM_FASTQ_KD (0 default; 1-6, 8 and 10 were retired)
 PARAM_INDEL_SORT = 8     # include/ganon.h GANON_PARAM_INDEL_SORT (0 segmented, 1 global)
 PARAM_PREP_LONG = 9      # include/ganon.h GANON_PARAM_PREP_LONG (-1 auto, 0 never, 1 always; at upload)
 PARAM_GROUP_OBS = 10     # include/ganon.h GANON_PARAM_GROUP_OBS (0 auto, 512, 1024)

@@ -125,12 +125,14 @@ GANON_API int ganon_ctx_set_variant(ganon_ctx *ctx, int variant);
  * whose reference range is all ACGT (1, default) or the nt16 reference only (0).
  * GANON_PARAM_FASTQ_KD: FASTQ formatter kernel: 0 (default) = 16-byte units with per-span window
  *   setup, 3 per lane in one load round; 13 / 14 = the same, 2 per lane, one / two 8 KiB tiles per
- *   workgroup; 16 / 9 / 10 = 16-byte units with per-unit setup (the default up to round 4), 2 / 1 / 3
- *   per lane; 11 = 16-byte units, 2 per lane, bases windows selected per output dword (A/B instance);
- *   12 = record rows; 1-6 or 8 = the dword kernel with that many output dwords per lane at once.
+ *   workgroup; 15 / 17 = as 0, a unit's span found by binary search / from a map entry per 8 units;
+ *   16 / 9 = 16-byte units with per-unit setup (the default up to round 4), 2 / 1 per lane; 11 =
+ *   16-byte units, 2 per lane, bases windows selected per output dword (A/B instance); 12 = record
+ *   rows. 1-6, 8 (the round-1 dword kernel) and 10 (3 quads per lane) were retired: GANON_E_ARG.
  * GANON_PARAM_FASTQ_SKIP (phase timing only, changes results): bit 0 leaves out the
- * formatter's source loads, bit 1 its stores; bits 3-6 stop after the descriptor scan / after the
- * dword map / leave out the interior pass / leave out the edge and constant bytes.
+ * formatter's source loads, bit 1 its stores; bits 3-5 stop after the descriptor scan / after the
+ * unit map / leave out the unit pass (the span and quad kernels; the row kernel reads bits 1 and 5,
+ * k_fq_dense none). Other bits are ignored.
  * GANON_PARAM_INDEL_SORT: the indel tally keeps only observations at positions where two or more
  * reads have an I/D op and sorts them per scope (0, default: segmented, 32-bit position keys), or
  * sorts every observation in one global sort of 64-bit scope|position keys (1). Same records.

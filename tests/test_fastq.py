@@ -83,14 +83,15 @@ def test_bad_for_reverse_flags_non_acgtn_reads():
 
 # ---- GPU: the HIP formatter ----------------------------------------------------------------
 
-@pytest.fixture(scope="module", params=[0, 15, 17, 13, 14, 16, 12, 9, 11, 3],
+@pytest.fixture(scope="module", params=[0, 15, 17, 13, 14, 16, 12, 9, 11],
                 ids=["span3", "span3_search", "span3_coarse", "span2", "span2_t2", "quad2", "rows", "quad1",
-                     "quad2_select", "dword3"])
+                     "quad2_select"])
 def masker(hip_built, request):
     """Every HIP formatter test runs on the span kernel (GANON_PARAM_FASTQ_KD 0, the default: 3 units
-    per lane; 13 / 14: 2 per lane, one / two 8 KiB tiles per workgroup), the quad kernel (16, the
-    default up to round 4; 9 = one quad per lane; 11 = the per-dword base select of round 1), the
-    record-row kernel (12) and the dword kernel (3)."""
+    per lane; 13 / 14: 2 per lane, one / two 8 KiB tiles per workgroup; 15 / 17: span found by search /
+    coarse map), the quad kernel (16, the default up to round 4; 9 = one quad per lane; 11 = the
+    per-dword base select of round 1) and the record-row kernel (12): every compiled instance. (The
+    round-1 dword kernel, which ran here as "dword3", is retired.)"""
     m = native.HipMasker(0)
     m.set_param(native.PARAM_FASTQ_KD, request.param)
     yield m
@@ -107,6 +108,38 @@ def test_hip_formatter_matches_oracle_edge_records(masker, seed):
 @pytest.mark.gpu
 def test_hip_formatter_tiny_records(masker):
     recs = _tiny_records()
+    assert masker.format_fastq(recs) == fastq_oracle.format_records(recs)
+
+
+@pytest.mark.gpu
+def test_hip_formatter_staging_threshold(masker):
+    """The hand-off at the tile kernels' staging limit: a tile touched by 64 records is the tile
+    kernel's own, one touched by 65 goes to k_fq_dense (every instance has this branch). 2,000
+    records of exactly 129 bytes (name 1, 60 bases, 60 qualities; half reverse; bases A, C, G, T, N)
+    put both kinds side by side: 16 tiles of 64 records, 15 of 65 and a last one of 32."""
+    n, L, tile = 2000, 60, 8192
+    rng = np.random.default_rng(12)
+    codes = rng.choice(np.array([1, 2, 4, 8, 15], np.uint8), n * L)
+    seq_len = np.full(n, L, np.int32)
+    name_len = np.ones(n, np.int32)
+    recs = {
+        "seq_bufs": [((codes[0::2] << 4) | codes[1::2]).astype(np.uint8)], "seq_sel": np.zeros(n, np.uint8),
+        "seq_nib_off": L * np.arange(n, dtype=np.int64), "seq_len": seq_len,
+        "reverse": (np.arange(n) % 2).astype(np.uint8),
+        "qual_bufs": [rng.integers(2, 41, n * L, dtype=np.uint8)], "qual_sel": np.zeros(n, np.uint8),
+        "qual_off": L * np.arange(n, dtype=np.int64), "qual_len": seq_len.copy(),
+        "qual_rev": np.zeros(n, np.uint8), "names": rng.integers(65, 91, n, dtype=np.uint8),
+        "name_off": np.arange(n, dtype=np.int64), "name_len": name_len, "mate": (1 + np.arange(n) % 2).astype(np.uint8),
+    }
+    # the records touching each 8 KiB output tile, from the record lengths (k_fq_off's tile_first restated)
+    end = np.cumsum(8 + name_len.astype(np.int64) + seq_len + recs["qual_len"])
+    assert np.all(np.diff(np.concatenate([[0], end])) == 129)
+    total = int(end[-1])
+    t0 = np.arange(0, total, tile, dtype=np.int64)
+    first = np.searchsorted(end, t0, side="right")                               # holds the tile's first byte
+    last = np.searchsorted(end, np.minimum(t0 + tile, total) - 1, side="right")  # holds its last byte
+    per_tile = last - first + 1
+    assert (per_tile == 64).sum() == 16 and (per_tile == 65).sum() == 15 and per_tile[-1] == 32
     assert masker.format_fastq(recs) == fastq_oracle.format_records(recs)
 
 

@@ -77,6 +77,28 @@ def test_retired_variants_are_rejected(masker):
     masker.set_variant(0)
 
 
+def test_retired_fastq_instances_are_rejected(masker):
+    """The formatter instances retired so far (GANON_PARAM_FASTQ_KD 1-6 and 8, the round-1 dword
+    kernel, and 10, three quads per lane): asking for one is an error that says so, values that never
+    meant anything stay errors, 0 is accepted, and a rejected value leaves the context formatting as
+    before. (9 and 11-17 still select compiled A/B instances: tests/test_fastq.py runs on each.)"""
+    import fastq_oracle
+    from genomeanonymizer_amd import native
+    from genomeanonymizer_amd.synth.batch import random_batch
+    from genomeanonymizer_amd.synth.fastq import fastq_records
+    for v in (1, 2, 3, 4, 5, 6, 8, 10):
+        with pytest.raises(native.GanonError, match="retired"):
+            masker.set_param(native.PARAM_FASTQ_KD, v)
+    for v in (-1, 7, 18):
+        with pytest.raises(native.GanonError):
+            masker.set_param(native.PARAM_FASTQ_KD, v)
+    masker.set_param(native.PARAM_FASTQ_KD, 0)
+    with pytest.raises(native.GanonError):
+        masker.set_param(native.PARAM_FASTQ_KD, 3)
+    recs = fastq_records(random_batch(3, n_scopes=10), seed=3, qual_rev_frac=0.3, name_len=(0, 30))
+    assert masker.format_fastq(recs) == fastq_oracle.format_records(recs)
+
+
 def test_reload_rebuilds_every_derived_array(masker, oracle):
     """ganon_batch_reload reuses the device buffers of another batch (grow-only): batch A, then
     a differently shaped batch B, then A again — every run rebuilds segments, groups and pieces

@@ -620,6 +620,13 @@ INF_FN int inflate_wave(InfShared &S, const uint8_t *g, int n, uint8_t *dst, int
         const uint8_t v = (uint8_t)b.take(8);
         if (lane == 0) S.out[w & M] = v;
       }
+      // (those bytes count towards the flush like any others: a run of stored blocks this short
+      // is served from the bit buffer alone and never reaches the loop below)
+      if (w - flushed >= kFlush) {
+        const int to = w & ~(kFlush - 1);
+        flush_out<NL>(S.out, dst, flushed, to, lane);
+        flushed = to;
+      }
       int rest = ln - k;
       if (b.pos + rest > n) return -kInfOverrun;
       while (rest > 0) {   // the rest from global memory, a flush chunk at a time

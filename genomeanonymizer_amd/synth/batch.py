@@ -45,7 +45,8 @@ def _cigar_word(op: str, n: int) -> int:
 def random_batch(seed: int, n_scopes: int = 64, max_reads: int = 40, read_len=(0, 220),
                  wide_scopes: int = 2, rare_frac: float = 0.02, wide_span=(20000, 40000)) -> Dict[str, np.ndarray]:
     """Edge-case batch. Every scope owns a private contig region so spans never collide. The
-    first ``wide_scopes`` scopes span ``wide_span`` positions (over 2^20: the huge-scope tile path)."""
+    first ``wide_scopes`` scopes span ``wide_span`` positions: 20-40 k by default, which stays with the
+    group kernels; only a ``wide_span`` over 2^20 reaches the huge-scope tile path."""
     rng = np.random.default_rng(seed)
     scopes = []
     region_len = []

@@ -1289,7 +1289,10 @@ GANON_API int ganon_indel_info(const ganon_indels *t, int64_t *info8) {
   info8[4] = t->n_candidates;
   info8[5] = t->n_rdist;
   info8[6] = t->global ? 1 : 0;
-  info8[7] = 0;
+  // the route the upload chose (the walk, the sort and the map of the filtered run)
+  info8[7] = (t->thread_walk ? GANON_INDEL_ROUTE_THREAD_WALK : 0) | (t->tsort ? GANON_INDEL_ROUTE_TSORT : 0) |
+             (t->gsort ? GANON_INDEL_ROUTE_GSORT : 0) |
+             (t->map_shift ? GANON_INDEL_ROUTE_HASHED | ((int64_t)(64 - t->map_shift) << 8) : 0);
   return GANON_OK;
 }
 

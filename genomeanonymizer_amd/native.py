@@ -77,6 +77,8 @@ INDEL_REC = np.dtype([("scope", np.int32), ("pos", np.int32), ("length", np.int3
                       ("rank", np.int32), ("kind", np.int32), ("read", np.int32), ("in_read_pos", np.int32)])
 INDEL_DEL, INDEL_INS = 2, 3
 INDEL_CALL, INDEL_SUPPORT = 0, 1
+# GANON_INDEL_ROUTE_* (ganon_indel_info's last slot)
+INDEL_ROUTE_THREAD_WALK, INDEL_ROUTE_TSORT, INDEL_ROUTE_GSORT, INDEL_ROUTE_HASHED = 1, 2, 4, 8
 
 
 def indel_records_array(rows) -> np.ndarray:
@@ -1330,8 +1332,14 @@ class DeviceIndels:
     def info(self) -> dict:
         a = np.zeros(8, np.int64)
         self.m._check(self.m._lib.ganon_indel_info(self.h, _ptr(a, _i64p)), "ganon_indel_info")
-        return dict(zip(("observations", "incidences", "key_bits", "records", "emitted", "reads", "global_sort"),
-                        a.tolist()))
+        d = dict(zip(("observations", "incidences", "key_bits", "records", "emitted", "reads", "global_sort"),
+                     a.tolist()))
+        # include/ganon.h GANON_INDEL_ROUTE_*: what the upload chose for the filtered run
+        route = int(a[7])
+        d.update(route=route & 0xF, thread_walk=bool(route & INDEL_ROUTE_THREAD_WALK),
+                 tsort=bool(route & INDEL_ROUTE_TSORT), gsort=bool(route & INDEL_ROUTE_GSORT),
+                 hashed_map=bool(route & INDEL_ROUTE_HASHED), map_log2_cells=(route >> 8) & 0xFF)
+        return d
 
     def free(self) -> None:
         if self.h:

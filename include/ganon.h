@@ -387,7 +387,17 @@ GANON_API int ganon_indel_run(ganon_ctx *ctx, ganon_indels *t);
 GANON_API int64_t ganon_indel_download(ganon_ctx *ctx, ganon_indels *t, ganon_indel_rec *out, int64_t cap);
 /* [observations, incidences with an I/D op, sort key bits, records (after download, else -1),
  *  observations emitted by the last run (after download, else -1: the candidate filter keeps only
- *  positions where two or more reads have an I/D op), reads with an I/D op, sort strategy, 0] */
+ *  positions where two or more reads have an I/D op), reads with an I/D op, sort strategy,
+ *  route]. route: what the upload chose from the batch's shape (and the A/B environment switches)
+ *  for the filtered run, GANON_INDEL_ROUTE_* below; GANON_PARAM_INDEL_SORT 1 uses neither the map
+ *  nor these sorts (sort strategy 1) and leaves the bits as planned. */
+enum {
+  GANON_INDEL_ROUTE_THREAD_WALK = 1, /* bit 0: a thread per read walks the CIGARs (else a wave per 256 ops) */
+  GANON_INDEL_ROUTE_TSORT = 2,       /* bit 1: in-place segment sort, 32-bit keys                           */
+  GANON_INDEL_ROUTE_GSORT = 4,       /* bit 2: one 64-bit radix sort of the capacity (neither sort bit:     */
+                                     /*        rocPRIM's segmented sort, 32-bit keys)                       */
+  GANON_INDEL_ROUTE_HASHED = 8       /* bit 3: hashed candidate map; bits 8-15: log2 of its cells (0 dense) */
+};
 GANON_API int ganon_indel_info(const ganon_indels *t, int64_t *info8);
 GANON_API int ganon_indel_free(ganon_ctx *ctx, ganon_indels *t);
 

@@ -39,6 +39,12 @@
 // position that shows a listed ALT becomes the reference base (ganon_known_sites.h, the host decoder's
 // rule). A thread per record — almost all leave after one lower bound —, a wave per record with more
 // than 48 CIGAR ops. Without a table nothing of this runs.
+//
+// Site discovery (--discover_sites, ganon_ctx_set_site_tally). With a device tally on the context
+// k_bam_site_tally runs after the scatter over the columns in device memory: the alleles the records of
+// one reference sequence show against the reference are OR-ed into a byte per position
+// (ganon_site_tally.h, the host decoder's rule). k_site_compact turns the bytes into the (pos, code)
+// list of the positions both datasets show one allele at. Without a tally nothing of this runs.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
@@ -325,6 +331,17 @@ struct ganon_bam_dcols {
   int64_t fixes = 0;            // failing chunks met by the checks (summed over the rounds)
 };
 
+// A device site tally (include/ganon.h): one reference sequence's nt16 bases and a byte per position,
+// both padded with zeros to whole compaction tiles, and after ganon_dtally_compact the site list.
+struct ganon_dtally {
+  int64_t len = 0, padded = 0;   // bases; bases rounded up to a multiple of kSiteTile
+  uint8_t *ref = nullptr;        // padded / 2 bytes
+  uint32_t *words = nullptr;     // padded bytes
+  int32_t *pos = nullptr;        // (after the compaction) n_sites positions and codes
+  uint8_t *code = nullptr;
+  int64_t n_sites = -1;
+};
+
 namespace {
 
 // Record i's columns and blob bytes, by one wave; src(k) = byte k of the record (its block_size
@@ -602,6 +619,129 @@ __global__ void __launch_bounds__(kBamThreads) k_bam_known_mask(ganon_bam_cols V
   if (threadIdx.x == 0 && s_cnt) atomicAdd(count, (unsigned long long)s_cnt);
 }
 
+// ---- --discover_sites: the evidence tally and its compaction ---------------------------------------------
+
+struct StView {
+  const uint8_t *ref;   // the sequence's nt16 bases from nibble 0 on
+  uint32_t *words;      // its tally bytes as dwords
+  int64_t len;
+  int32_t tid;          // the BAM sequence id whose records are evidence
+  int32_t dataset;
+};
+
+// ganon_st's store on the device: one relaxed agent-scope atomic OR on the aligned word that holds the
+// position's byte (four positions share a word, records of other workgroups write them).
+struct StStore {
+  uint32_t *words;
+  __device__ __forceinline__ void operator()(int64_t r, uint8_t bits) {
+    __hip_atomic_fetch_or(words + (r >> 2), (uint32_t)bits << (8 * (int)(r & 3)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+
+// One record with a long CIGAR, by one wave (every lane active): 64 ops at a time, their reference and
+// query starts from prefix sums (ks_incl_sum: the lengths in two 14-bit halves); a lane with an M / = /
+// X op tallies its op's bases (ganon_st::tally_span clips them to the read and the sequence).
+__device__ __forceinline__ void st_tally_wave(const StView &T, int lane, int32_t pos, int32_t ncig, int32_t lseq,
+                                              const uint32_t *__restrict__ cig, const uint8_t *__restrict__ seq) {
+  const ganon_st::Ref R{T.ref, 0, T.len};
+  StStore st{T.words};
+  int64_t r = pos, q = 0;
+  for (int k0 = 0; k0 < ncig && q < lseq && r < T.len; k0 += 64) {   // (wave-uniform)
+    const uint32_t w = k0 + lane < ncig ? cig[k0 + lane] : 0u;
+    const int op = (int)(w & 15u);
+    const uint32_t len = w >> 4;
+    const bool m = op == 0 || op == 7 || op == 8;
+    const uint32_t rl = (m || op == 2 || op == 3) ? len : 0u, ql = (m || op == 1 || op == 4) ? len : 0u;
+    int64_t rt, qt;
+    const int64_t r0 = r + ks_incl_sum(rl, rt) - rl, q0 = q + ks_incl_sum(ql, qt) - ql;
+    if (m && len) ganon_st::tally_span(R, seq, lseq, r0, q0, (int64_t)len, 4 * T.dataset, st);
+    r += rt;
+    q += qt;
+  }
+}
+
+// The tally of --discover_sites over the decoded columns (ganon_site_tally.h has the rule). A thread per
+// record of sequence T.tid that the rule does not skip: it walks its CIGAR and compares eight bases a
+// step, a dword of read nibbles XOR a dword of reference nibbles (ganon_st::nib8), and goes nibble by
+// nibble only inside a word that differs: mismatches are about 0.1-1 % of the bases, the atomic ORs are
+// rare. Records with more than kKsLongOps ops are listed in LDS and taken a wave each after the
+// barrier (st_tally_wave), as k_bam_known_mask does and for the same reason: one thread on a
+// thousand-op CIGAR would hold its wave.
+__global__ void __launch_bounds__(kBamThreads) k_bam_site_tally(ganon_bam_cols V, int64_t nr, StView T) {
+  __shared__ int s_long[kBamThreads];
+  __shared__ int s_nlong;
+  if (threadIdx.x == 0) s_nlong = 0;
+  __syncthreads();
+  const int64_t i0 = (int64_t)blockIdx.x * kBamThreads;
+  const int64_t i = i0 + threadIdx.x;
+  if (i < nr && V.tid[i] == T.tid) {
+    const int32_t flag = V.flag[i], ncig = V.n_cigar[i], lseq = V.l_seq[i];
+    if (!(flag & 4) && ncig > 0 && lseq > 0) {
+      if (ncig > kKsLongOps) {
+        s_long[atomicAdd(&s_nlong, 1)] = (int)threadIdx.x;
+      } else {
+        const ganon_st::Ref R{T.ref, 0, T.len};
+        StStore st{T.words};
+        ganon_st::tally_record(R, V.pos[i], ncig, lseq, V.cigar + V.cig_off[i], V.seq + V.seq_off[i], T.dataset, st);
+      }
+    }
+  }
+  __syncthreads();
+  const int nlong = s_nlong, lane = threadIdx.x & 63;
+  for (int k = threadIdx.x >> 6; k < nlong; k += kBamThreads / 64) {   // (wave-uniform)
+    const int64_t g = i0 + s_long[k];
+    st_tally_wave(T, lane, V.pos[g], V.n_cigar[g], V.l_seq[g], V.cigar + V.cig_off[g], V.seq + V.seq_off[g]);
+  }
+}
+
+constexpr int kSiteTile = 8 * kBamThreads;   // positions per workgroup of k_site_compact: eight a thread
+
+// The sites of a tally: a thread takes eight positions (two dwords of tally bytes, OR-ed with the host
+// tally's where the host side touched the sequence), alt = low & high nibble per byte. Write false:
+// the tile's site count to count[tile]. Write true: the sites at base[tile] (the scanned counts) plus
+// the block's exclusive prefix, in position order, the reference nibble from the sequence's nt16.
+template <bool Write>
+__global__ void __launch_bounds__(kBamThreads) k_site_compact(const uint32_t *__restrict__ words,
+                                                              const uint32_t *__restrict__ host_words,
+                                                              const uint8_t *__restrict__ ref, int64_t *__restrict__ count,
+                                                              const int64_t *__restrict__ base, int32_t *__restrict__ pos,
+                                                              uint8_t *__restrict__ code) {
+  __shared__ int s_wave[kBamThreads / 64];
+  const int64_t p0 = (int64_t)blockIdx.x * kSiteTile + 8 * (int64_t)threadIdx.x;
+  uint2 w = *reinterpret_cast<const uint2 *>(words + (p0 >> 2));
+  if (host_words) {
+    const uint2 h = *reinterpret_cast<const uint2 *>(host_words + (p0 >> 2));
+    w.x |= h.x;
+    w.y |= h.y;
+  }
+  const uint32_t a0 = w.x & (w.x >> 4) & 0x0F0F0F0Fu, a1 = w.y & (w.y >> 4) & 0x0F0F0F0Fu;
+  int cnt = 0;
+  for (int j = 0; j < 4; ++j) cnt += ((a0 >> (8 * j)) & 15u ? 1 : 0) + ((a1 >> (8 * j)) & 15u ? 1 : 0);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int incl = ganon_wave::incl_sum(cnt);
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int before = 0, total = 0;
+  for (int k = 0; k < kBamThreads / 64; ++k) {
+    if (k < wave) before += s_wave[k];
+    total += s_wave[k];
+  }
+  if (!Write) {
+    if (threadIdx.x == 0) count[blockIdx.x] = total;
+    return;
+  }
+  if (!cnt) return;
+  int64_t o = base[blockIdx.x] + before + incl - cnt;
+  const uint32_t rf = __builtin_bswap32(*reinterpret_cast<const uint32_t *>(ref + (p0 >> 1)));   // base j: bits 31 - 4j ..
+  for (int j = 0; j < 8; ++j) {
+    const uint32_t alt = ((j < 4 ? a0 : a1) >> (8 * (j & 3))) & 15u;
+    if (!alt) continue;
+    pos[o] = (int32_t)(p0 + j);
+    code[o] = (uint8_t)((((rf >> (28 - 4 * j)) & 15u) << 4) | alt);
+    ++o;
+  }
+}
+
 unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBamThreads - 1) / kBamThreads); }
 
 template <typename T>
@@ -870,6 +1010,15 @@ int columns(ganon_ctx *ctx, const uint8_t *d, int64_t p, int64_t n, ganon_bam_dc
     }
     if ((rc = check_launch(ctx, "k_bam_known_mask"))) return rc;
   }
+  if (nr && ctx->st_tally) {   // --discover_sites: the evidence of the columns just written
+    const ganon_dtally *D = ctx->st_tally;
+    const StView T{D->ref, D->words, D->len, ctx->st_tid, ctx->st_dataset};
+    {
+      ganon_detail::KernelScope ks(ctx, "k_bam_site_tally");
+      hipLaunchKernelGGL(k_bam_site_tally, dim3(grid_of(nr)), dim3(kBamThreads), 0, s, V, nr, T);
+    }
+    if ((rc = check_launch(ctx, "k_bam_site_tally"))) return rc;
+  }
   return ganon_batch_sync(ctx);   // (collects the kernel times when profiling)
 }
 
@@ -1004,6 +1153,154 @@ GANON_API int ganon_ctx_known_sites_masked(ganon_ctx *ctx, int64_t *masked) {
   if (!ctx || !masked) return fail(ctx, GANON_E_ARG, "ganon_ctx_known_sites_masked: bad arguments");
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
   return ks_collect(ctx, masked);
+}
+
+GANON_API int ganon_site_compact_tile(void) { return kSiteTile; }
+
+static void dtally_release(ganon_dtally *D) {
+  if (!D) return;
+  hipFree(D->ref);   // (hipFree waits for the device: no kernel reads them any more)
+  hipFree(D->words);
+  hipFree(D->pos);
+  hipFree(D->code);
+  delete D;
+}
+
+GANON_API int ganon_dtally_create(ganon_ctx *ctx, const uint8_t *ref_nt16, int64_t len, ganon_dtally **out) {
+  if (!ctx || !out || len < 0 || len > INT32_MAX || (len > 0 && !ref_nt16))
+    return fail(ctx, GANON_E_ARG, "ganon_dtally_create: bad arguments");
+  *out = nullptr;
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
+  auto *D = new ganon_dtally();
+  D->len = len;
+  D->padded = std::max<int64_t>(1, (len + kSiteTile - 1) / kSiteTile) * kSiteTile;
+  hipStream_t s = ctx->stream;
+  if (hipMalloc(reinterpret_cast<void **>(&D->ref), (size_t)D->padded / 2) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void **>(&D->words), (size_t)D->padded) != hipSuccess ||
+      hipMemsetAsync(D->ref, 0, (size_t)D->padded / 2, s) != hipSuccess ||
+      hipMemsetAsync(D->words, 0, (size_t)D->padded, s) != hipSuccess ||
+      (len > 0 && hipMemcpyAsync(D->ref, ref_nt16, (size_t)((len + 1) / 2), hipMemcpyHostToDevice, s) != hipSuccess) ||
+      ganon_detail::sync_stream(s) != hipSuccess) {
+    ganon_detail::sync_stream(s);
+    dtally_release(D);
+    return fail(ctx, GANON_E_DEVICE, "ganon_dtally_create: device allocation or upload of %lld bases failed", (long long)len);
+  }
+  *out = D;
+  return GANON_OK;
+}
+
+GANON_API int ganon_ctx_set_site_tally(ganon_ctx *ctx, ganon_dtally *tally, int32_t dataset, int32_t tid) {
+  if (!ctx) return GANON_E_ARG;
+  if (tally && (dataset < 0 || dataset > 1 || tid < 0))
+    return fail(ctx, GANON_E_ARG, "ganon_ctx_set_site_tally: dataset is 0 (tumor) or 1 (normal), tid a BAM sequence id");
+  if (tally && tally->n_sites >= 0) return fail(ctx, GANON_E_STATE, "ganon_ctx_set_site_tally: the tally is compacted already");
+  ctx->st_tally = tally;
+  ctx->st_dataset = tally ? dataset : 0;
+  ctx->st_tid = tally ? tid : -1;
+  return GANON_OK;
+}
+
+GANON_API int ganon_dtally_compact(ganon_ctx *ctx, ganon_dtally *D, const uint8_t *host_bytes, int64_t *n) {
+  if (!ctx || !D || !n) return fail(ctx, GANON_E_ARG, "ganon_dtally_compact: bad arguments");
+  if (D->n_sites >= 0) return fail(ctx, GANON_E_STATE, "ganon_dtally_compact: compacted already");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
+  hipStream_t s = ctx->stream;
+  if (ctx->profiling) {   // a profiled call: ganon_last_kernel_times reports this call's kernels alone
+    ganon_detail::sync_stream(s);
+    for (auto &r : ctx->recs) {
+      ctx->pool.push_back(r.e0);
+      ctx->pool.push_back(r.e1);
+    }
+    ctx->recs.clear();
+  }
+  const int64_t tiles = D->padded / kSiteTile;
+  std::vector<std::pair<void *, size_t>> tmp;
+  auto dalloc = [&](size_t bytes) -> void * {
+    void *q = nullptr;
+    size_t got = 0;
+    if (ctx_dmalloc(ctx, &q, std::max<size_t>(bytes, 256), &got) != hipSuccess) return nullptr;
+    tmp.emplace_back(q, got);
+    return q;
+  };
+  struct Free {
+    ganon_ctx *ctx;
+    hipStream_t s;
+    std::vector<std::pair<void *, size_t>> &t;
+    ~Free() {
+      ganon_detail::sync_stream(s);
+      for (auto &q : t) ctx_dfree(ctx, q.first, q.second);
+    }
+  } free_tmp{ctx, s, tmp};
+  int rc;
+  uint32_t *hw = nullptr;
+  if (host_bytes && D->len > 0) {
+    hw = static_cast<uint32_t *>(dalloc((size_t)D->padded));
+    if (!hw) return fail(ctx, GANON_E_DEVICE, "ganon_dtally_compact: device allocation failed");
+    HIP_OR_FAIL(hipMemsetAsync(hw, 0, (size_t)D->padded, s));
+    HIP_OR_FAIL(hipMemcpyAsync(hw, host_bytes, (size_t)D->len, hipMemcpyHostToDevice, s));
+    HIP_OR_FAIL(ganon_detail::sync_stream(s));   // (the kernel events time the compaction, not the copy)
+  }
+  int64_t *count = static_cast<int64_t *>(dalloc((size_t)(tiles + 1) * 8));
+  int64_t *base = static_cast<int64_t *>(dalloc((size_t)(tiles + 1) * 8));
+  size_t tb = 0;
+  HIP_OR_FAIL(rocprim::exclusive_scan(nullptr, tb, count, base, (int64_t)0, (size_t)(tiles + 1), rocprim::plus<int64_t>(), s));
+  void *tsc = dalloc(tb);
+  if (!count || !base || !tsc) return fail(ctx, GANON_E_DEVICE, "ganon_dtally_compact: device allocation failed");
+  HIP_OR_FAIL(hipMemsetAsync(count + tiles, 0, 8, s));
+  {
+    ganon_detail::KernelScope ks(ctx, "k_site_compact");
+    hipLaunchKernelGGL(k_site_compact<false>, dim3((unsigned)tiles), dim3(kBamThreads), 0, s, D->words, hw, D->ref, count,
+                       base, nullptr, nullptr);
+  }
+  if ((rc = check_launch(ctx, "k_site_compact"))) return rc;
+  {
+    ganon_detail::KernelScope ks(ctx, "site_scan");
+    HIP_OR_FAIL(rocprim::exclusive_scan(tsc, tb, count, base, (int64_t)0, (size_t)(tiles + 1), rocprim::plus<int64_t>(), s));
+  }
+  int64_t total = 0;
+  HIP_OR_FAIL(ganon_detail::readback(&total, base + tiles, 8, s));
+  HIP_OR_FAIL(ganon_detail::sync_stream(s));
+  if (total < 0 || total > D->len) return fail(ctx, GANON_E_STATE, "ganon_dtally_compact: site count out of range");
+  if (total) {
+    HIP_OR_FAIL(hipMalloc(reinterpret_cast<void **>(&D->pos), (size_t)total * 4));
+    HIP_OR_FAIL(hipMalloc(reinterpret_cast<void **>(&D->code), (size_t)total));
+    {
+      ganon_detail::KernelScope ks(ctx, "k_site_compact");
+      hipLaunchKernelGGL(k_site_compact<true>, dim3((unsigned)tiles), dim3(kBamThreads), 0, s, D->words, hw, D->ref, count,
+                         base, D->pos, D->code);
+    }
+    if ((rc = check_launch(ctx, "k_site_compact"))) return rc;
+  }
+  if ((rc = ganon_batch_sync(ctx))) return rc;   // (collects the kernel times when profiling)
+  D->n_sites = total;
+  *n = total;
+  return GANON_OK;
+}
+
+GANON_API int ganon_dtally_sites(ganon_ctx *ctx, ganon_dtally *D, int32_t *pos, uint8_t *code) {
+  if (!ctx || !D) return fail(ctx, GANON_E_ARG, "ganon_dtally_sites: bad arguments");
+  if (D->n_sites < 0) return fail(ctx, GANON_E_STATE, "ganon_dtally_sites: before ganon_dtally_compact");
+  if (D->n_sites == 0) return GANON_OK;
+  if (!pos || !code) return fail(ctx, GANON_E_ARG, "ganon_dtally_sites: bad arguments");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
+  HIP_OR_FAIL(hipMemcpyAsync(pos, D->pos, (size_t)D->n_sites * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_OR_FAIL(hipMemcpyAsync(code, D->code, (size_t)D->n_sites, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_OR_FAIL(ganon_detail::sync_stream(ctx->stream));
+  return GANON_OK;
+}
+
+GANON_API int ganon_dtally_free(ganon_ctx *ctx, ganon_dtally *D) {
+  if (!D) return GANON_OK;
+  if (ctx) {
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
+    if (ctx->st_tally == D) {
+      ctx->st_tally = nullptr;
+      ctx->st_tid = -1;
+    }
+    ganon_detail::sync_stream(ctx->stream);
+  }
+  dtally_release(D);
+  return GANON_OK;
 }
 
 GANON_API int ganon_bam_dcols_get(const ganon_bam_dcols *c, ganon_bam_cols *device_view, int64_t *fixes) {

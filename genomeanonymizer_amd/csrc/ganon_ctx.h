@@ -19,6 +19,9 @@
 #include "../../include/ganon.h"
 #include "ganon_name_hash.h"
 #include "ganon_known_sites.h"
+#include "ganon_site_tally.h"
+
+struct ganon_dtally;                               // ganon_bam.hip: a device site tally
 
 struct ganon_inflate_state;                       // ganon_inflate.hip: grow-only device buffers
 void ganon_inflate_free(ganon_inflate_state *st);
@@ -76,6 +79,10 @@ struct ganon_ctx {
   ganon_ks::View ks_view{};
   unsigned long long *ks_count = nullptr;   // (device) bases rewritten since the table was set
   int64_t ks_total = 0;                     // ... and by the tables this context held before
+  // ganon_ctx_set_site_tally (--discover_sites): the tally k_bam_site_tally ORs the decoded records of
+  // BAM sequence st_tid into, as dataset st_dataset; nullptr: no tally, no kernel
+  ganon_dtally *st_tally = nullptr;
+  int32_t st_dataset = 0, st_tid = -1;
   // GANON_INDEL_FORK=1: the indel tally of a batch runs on a side stream forked after the batch's
   // prep (fork_ev, recorded by ganon_batch_run before the group kernel) and joined back (join_ev), so
   // that its latency-bound launches overlap the bandwidth-bound group kernel (they read only the

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <string>
 #include <memory>
+#include <mutex>
 #include <thread>
 #include <utility>
 #include <vector>
@@ -21,6 +22,7 @@
 #include "../../include/ganon_host.h"
 #include "ganon_name_hash.h"
 #include "ganon_known_sites.h"
+#include "ganon_site_tally.h"
 
 namespace {
 
@@ -206,6 +208,60 @@ struct ganon_sites {
   std::shared_ptr<const SitesData> data;
 };
 
+// --discover_sites: the evidence tally (ganon_site_tally.h) of one run's sequences, a byte array per
+// sequence made zeroed when the first evidence on it arrives; shared by the handle and every reader it
+// was set on. Threads of several readers OR into one array: an atomic OR on the byte.
+struct TallyData {
+  const uint8_t *nt16 = nullptr;   // the caller's packed genome (kept alive by the caller)
+  std::vector<int64_t> off, len;   // per sequence: nibble offset in nt16 (-1: not in the FASTA), bases
+  std::vector<std::atomic<uint8_t *>> bytes;
+  std::atomic<bool> failed{false};   // an array could not be allocated
+  std::mutex mu;
+  explicit TallyData(size_t n) : bytes(n) {
+    for (auto &b : bytes) b.store(nullptr, std::memory_order_relaxed);
+  }
+  TallyData(const TallyData &) = delete;
+  TallyData &operator=(const TallyData &) = delete;
+  ~TallyData() {
+    for (auto &b : bytes) std::free(b.load());
+  }
+  uint8_t *touch(int32_t s) {
+    uint8_t *p = bytes[(size_t)s].load(std::memory_order_acquire);
+    if (p) return p;
+    std::lock_guard<std::mutex> g(mu);
+    p = bytes[(size_t)s].load(std::memory_order_acquire);
+    if (!p) {
+      p = static_cast<uint8_t *>(std::calloc((size_t)std::max<int64_t>(len[(size_t)s], 1), 1));
+      if (!p) failed.store(true);
+      bytes[(size_t)s].store(p, std::memory_order_release);
+    }
+    return p;
+  }
+  void release(int32_t s) {
+    std::lock_guard<std::mutex> g(mu);
+    std::free(bytes[(size_t)s].exchange(nullptr));
+  }
+};
+struct ganon_site_tally {
+  std::shared_ptr<TallyData> data;
+};
+// A tally as one decoder uses it: the dataset its records belong to (0 tumor, 1 normal) and the tally's
+// sequence of each BAM sequence id of its file (-1: none).
+struct TallyUse {
+  std::shared_ptr<TallyData> data;
+  int dataset = 0;
+  std::vector<int32_t> slot_of_tid;
+};
+struct TallyStore {   // ganon_st's store on the host: the array on the first evidence, an atomic OR on the byte
+  TallyData *T;
+  int32_t slot;
+  uint8_t *p;
+  void operator()(int64_t r, uint8_t bits) {
+    if (!p && !(p = T->touch(slot))) return;
+    if ((__atomic_load_n(p + r, __ATOMIC_RELAXED) & bits) != bits) __atomic_fetch_or(p + r, bits, __ATOMIC_RELAXED);
+  }
+};
+
 namespace {
 
 // One BGZF block at h (avail bytes from h to the end of the buffer). Returns 1 with the block's
@@ -301,10 +357,11 @@ int parse_header(const uint8_t *d, int64_t n, ganon_bam *bam, int64_t &p) {
 // hash: 32 hex characters and a NUL, name_off[i] = 33 i; the hash runs on the name pass's threads.
 // With sites (--known_sites) the panel mask (ganon_known_sites.h) rewrites each record's bases, and
 // with a quality their quality bytes, in the table right after they are copied, on the same threads;
-// bam->known_masked counts the rewritten bases.
+// bam->known_masked counts the rewritten bases. With tally (--discover_sites) each record's evidence is
+// OR-ed into the tally (ganon_site_tally.h) at the same place, before any mask.
 int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, int threads,
                        const std::vector<int64_t> *known = nullptr, const ganon_nh::KeyState *ks = nullptr,
-                       const ganon_ks::View *sites = nullptr) {
+                       const ganon_ks::View *sites = nullptr, const TallyUse *tally = nullptr) {
   const int nt = std::max(1, std::min(threads, 64));
   // ---- records: boundaries (sequential), sizes + offsets, then columns in parallel ----
   std::vector<int64_t> own;   // offset of each record's block_size field
@@ -434,6 +491,15 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
       bam->aux_off[i] = o_aux[i];
       bam->aux_len[i] = (int32_t)(bs - q);
       copy_bytes(bam->aux.data() + o_aux[i], r + q, (size_t)(bs - q));
+      if (tally && !ganon_st::skips((int32_t)tally->slot_of_tid.size(), rtid, rflag, ncig, lseq)) {
+        const int32_t slot = tally->slot_of_tid[(size_t)rtid];
+        TallyData *T = tally->data.get();
+        if (slot >= 0 && T->off[(size_t)slot] >= 0) {
+          const ganon_st::Ref R{T->nt16, T->off[(size_t)slot], T->len[(size_t)slot]};
+          TallyStore st{T, slot, nullptr};
+          ganon_st::tally_record(R, rpos, ncig, lseq, cg, bam->seq.data() + o_seq[i], tally->dataset, st);
+        }
+      }
       if (sites)
         mine += ganon_ks::mask_record(*sites, rtid, rpos, rflag, ncig, lseq, cg, bam->seq.data() + o_seq[i],
                                       bam->qual.data() + o_qual[i]);
@@ -442,6 +508,7 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
   });
   bam->known_masked += masked.load();
   lap(kPhColumns, tph);
+  if (tally && tally->data->failed.load()) return set_err("out of memory allocating a site tally");
   return 0;
 }
 
@@ -449,7 +516,7 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
 }  // namespace
 
 static int bam_open_impl(const char *path, int threads, ganon_bam **out, const ganon_nh::KeyState *ks = nullptr,
-                         const ganon_ks::View *sites = nullptr) {
+                         const ganon_ks::View *sites = nullptr, const TallyUse *tally = nullptr) {
   FILE *fh = std::fopen(path, "rb");
   if (!fh) return set_err(std::string("cannot open ") + path);
   std::fseek(fh, 0, SEEK_END);
@@ -486,7 +553,7 @@ static int bam_open_impl(const char *path, int threads, ganon_bam **out, const g
     delete bam;
     return hr < 0 ? -1 : set_err("truncated header");
   }
-  if (records_to_columns(data.data(), p, (int64_t)data.size(), bam, threads, nullptr, ks, sites) != 0) {
+  if (records_to_columns(data.data(), p, (int64_t)data.size(), bam, threads, nullptr, ks, sites, tally) != 0) {
     delete bam;
     return -1;
   }
@@ -578,6 +645,107 @@ GANON_HOST_API int ganon_bam_open_ex(const char *path, int threads, const uint8_
 }
 
 GANON_HOST_API int64_t ganon_bam_known_sites_masked(const ganon_bam *b) { return b ? b->known_masked : 0; }
+
+GANON_HOST_API int ganon_site_tally_create(int32_t n_seq, const uint8_t *nt16, const int64_t *nib_off, const int64_t *len,
+                                           ganon_site_tally **out) {
+  if (!out) return set_err("null argument");
+  *out = nullptr;
+  if (n_seq < 0 || (n_seq > 0 && (!nib_off || !len))) return set_err("ganon_site_tally_create: bad arguments");
+  for (int32_t s = 0; s < n_seq; ++s)
+    if (len[s] < 0 || len[s] > INT32_MAX || nib_off[s] < -1 || (nib_off[s] >= 0 && len[s] > 0 && !nt16))
+      return set_err("ganon_site_tally_create: a sequence's length is 0..2^31-1, its nibble offset >= 0 or -1");
+  try {
+    auto d = std::make_shared<TallyData>((size_t)n_seq);
+    d->nt16 = nt16;
+    d->off.assign(nib_off, nib_off + n_seq);
+    d->len.assign(len, len + n_seq);
+    *out = new ganon_site_tally{std::move(d)};
+    return 0;
+  } catch (const std::bad_alloc &) {
+    return set_err("out of memory making a site tally");
+  }
+}
+
+GANON_HOST_API void ganon_site_tally_destroy(ganon_site_tally *t) { delete t; }
+
+static bool tally_slot_ok(const ganon_site_tally *t, int32_t s) { return t && s >= 0 && s < (int32_t)t->data->len.size(); }
+
+GANON_HOST_API const uint8_t *ganon_site_tally_bytes(const ganon_site_tally *t, int32_t seq) {
+  return tally_slot_ok(t, seq) ? t->data->bytes[(size_t)seq].load(std::memory_order_acquire) : nullptr;
+}
+
+GANON_HOST_API int64_t ganon_site_tally_count(const ganon_site_tally *t, int32_t seq) {
+  if (!tally_slot_ok(t, seq)) return -1;
+  const TallyData &T = *t->data;
+  const uint8_t *b = T.bytes[(size_t)seq].load(std::memory_order_acquire);
+  if (!b) return 0;
+  return ganon_st::compact(ganon_st::Ref{T.nt16, T.off[(size_t)seq], T.len[(size_t)seq]}, b, T.len[(size_t)seq], nullptr,
+                           nullptr);
+}
+
+GANON_HOST_API int64_t ganon_site_tally_finish(ganon_site_tally *t, int32_t seq, int32_t *pos, uint8_t *code, int64_t cap) {
+  if (!tally_slot_ok(t, seq)) {
+    set_err("ganon_site_tally_finish: no such sequence");
+    return -1;
+  }
+  TallyData &T = *t->data;
+  const uint8_t *b = T.bytes[(size_t)seq].load(std::memory_order_acquire);
+  int64_t n = 0;
+  if (b) {
+    const ganon_st::Ref R{T.nt16, T.off[(size_t)seq], T.len[(size_t)seq]};
+    n = ganon_st::compact(R, b, T.len[(size_t)seq], nullptr, nullptr);
+    if (n > cap || (n > 0 && (!pos || !code))) {
+      set_err("ganon_site_tally_finish: the arrays are too small (ganon_site_tally_count gives the number)");
+      return -1;
+    }
+    ganon_st::compact(R, b, T.len[(size_t)seq], pos, code);
+  }
+  T.release(seq);
+  return n;
+}
+
+GANON_HOST_API void ganon_site_tally_release(ganon_site_tally *t, int32_t seq) {
+  if (tally_slot_ok(t, seq)) t->data->release(seq);
+}
+
+// The checked use of a tally by one decoder (nullptr with the error set).
+static std::unique_ptr<TallyUse> tally_use(const ganon_site_tally *t, int32_t dataset, const int32_t *seq_of_tid,
+                                           int32_t n_tid) {
+  if (dataset < 0 || dataset > 1 || n_tid < 0 || (n_tid > 0 && !seq_of_tid)) {
+    set_err("site tally: dataset is 0 (tumor) or 1 (normal), seq_of_tid has an entry per BAM sequence");
+    return nullptr;
+  }
+  for (int32_t i = 0; i < n_tid; ++i)
+    if (seq_of_tid[i] < -1 || seq_of_tid[i] >= (int32_t)t->data->len.size()) {
+      set_err("site tally: seq_of_tid names a sequence the tally does not have");
+      return nullptr;
+    }
+  auto u = std::make_unique<TallyUse>();
+  u->data = t->data;
+  u->dataset = dataset;
+  u->slot_of_tid.assign(seq_of_tid, seq_of_tid + n_tid);
+  return u;
+}
+
+GANON_HOST_API int ganon_bam_open_ex2(const char *path, int threads, const uint8_t *key, int32_t key_len,
+                                      const ganon_sites *sites, const ganon_site_tally *tally, int32_t dataset,
+                                      const int32_t *seq_of_tid, int32_t n_tid, ganon_bam **out) {
+  if (!path || !out) return set_err("null argument");
+  *out = nullptr;
+  if (key_len < 0 || key_len > ganon_nh::kMaxKey || (key_len > 0 && !key))
+    return set_err("ganon_bam_open_ex2: a key of 1..32 bytes, or length 0 for none");
+  ganon_nh::KeyState ks;
+  if (key_len > 0) ganon_nh::key_state(key, key_len, &ks);
+  try {
+    std::unique_ptr<TallyUse> use;
+    if (tally && !(use = tally_use(tally, dataset, seq_of_tid, n_tid))) return -1;
+    return bam_open_impl(path, threads, out, key_len > 0 ? &ks : nullptr, sites ? &sites->data->view : nullptr, use.get());
+  } catch (const std::bad_alloc &) {
+    return set_err("out of memory decoding the BAM file");
+  } catch (const std::exception &e) {
+    return set_err(std::string("BAM decode failed: ") + e.what());
+  }
+}
 
 GANON_HOST_API int ganon_names_hash(const char *names, const int64_t *off, const int32_t *len, int64_t n,
                                     const uint8_t *key, int32_t key_len, int threads, char *out) {
@@ -695,6 +863,7 @@ struct ganon_bam_reader {
   ganon_nh::KeyState name_key{};
   std::shared_ptr<const SitesData> sites;   // ganon_bam_reader_set_known_sites: the panel mask of its tables
   int64_t known_masked = 0;                 // ... and the bases its host decodes rewrote so far
+  std::unique_ptr<TallyUse> tally;          // ganon_bam_reader_set_site_tally: the evidence tally of its tables
 };
 
 namespace {
@@ -1188,6 +1357,25 @@ GANON_HOST_API int ganon_bam_reader_set_known_sites(ganon_bam_reader *R, const g
 
 GANON_HOST_API int64_t ganon_bam_reader_known_sites_masked(const ganon_bam_reader *R) { return R ? R->known_masked : 0; }
 
+GANON_HOST_API int ganon_bam_reader_set_site_tally(ganon_bam_reader *R, const ganon_site_tally *tally, int32_t dataset,
+                                                   const int32_t *seq_of_tid, int32_t n_tid) {
+  if (!R) return set_err("null argument");
+  if (!tally) {
+    R->tally.reset();
+    return 0;
+  }
+  if (n_tid != (int32_t)R->header.ref_len.size())
+    return set_err("ganon_bam_reader_set_site_tally: seq_of_tid has an entry per sequence of the BAM header");
+  try {
+    auto u = tally_use(tally, dataset, seq_of_tid, n_tid);
+    if (!u) return -1;
+    R->tally = std::move(u);
+    return 0;
+  } catch (const std::bad_alloc &) {
+    return set_err("out of memory setting a site tally");
+  }
+}
+
 GANON_HOST_API int ganon_bam_reader_has_index(const ganon_bam_reader *R) { return R && R->has_index ? 1 : 0; }
 
 GANON_HOST_API int ganon_bam_reader_header(ganon_bam_reader *R, ganon_bam_view *v) {
@@ -1232,7 +1420,7 @@ GANON_HOST_API int ganon_bam_reader_contig(ganon_bam_reader *R, int32_t tid, gan
     bam->ref_name_off = R->header.ref_name_off;
     bam->ref_len = R->header.ref_len;
     if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs, R->hashed ? &R->name_key : nullptr,
-                           R->sites ? &R->sites->view : nullptr) != 0) {
+                           R->sites ? &R->sites->view : nullptr, R->tally.get()) != 0) {
       delete bam;
       return -1;
     }
@@ -1294,7 +1482,7 @@ GANON_HOST_API int ganon_bam_reader_region(ganon_bam_reader *R, int32_t tid, int
       return 0;
     }
     if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs, R->hashed ? &R->name_key : nullptr,
-                           R->sites ? &R->sites->view : nullptr) != 0) {
+                           R->sites ? &R->sites->view : nullptr, R->tally.get()) != 0) {
       delete bam;
       return -1;
     }

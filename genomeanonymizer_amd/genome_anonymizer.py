@@ -3,6 +3,7 @@
   python -m genomeanonymizer_amd.genome_anonymizer -d DIR -s samples.tsv -r ref.fa \\
       [-m complete_germline] [-c CPUS] [--record_statistics] [--enhanced_multiprocessing] [-v N]
       [--compress_output] [--masked_base_quality Q] [--hash_read_names] [--known_sites PANEL.vcf[.gz]]
+      [--discover_sites]
 
 samples.tsv: tumor<TAB>normal<TAB>vcf per line, paths relative to DIR, '#' lines skipped.
 Outputs next to the inputs: re.sub('.bam|.sam|.cram', '.anonymized', path) + .1/.2.fastq
@@ -34,6 +35,19 @@ the panel for that pair: those calls are what the product keeps. With --masked_b
 rewritten bases are printed with quality Q too. Limits: a supplementary record is masked along its own
 alignment, the primary's soft-clipped copy of those bases is not; indels and MNVs of the panel are not
 used. Each process logs how many bases it rewrote.
+--discover_sites (an extension; --no-discover_sites; GANON_DISCOVER_SITES=1 is the same default): the
+panel the pair's own BAMs give. Before a pair's jobs start a pre-pass decodes both BAMs once more and
+notes, per reference position, which alleles other than the reference's the tumor reads and the normal
+reads show (aligned bases only — CIGAR M, =, X —, A, C, G, T against a reference A, C, G, T; no quality,
+depth or strand filter: one tumor read and one normal read are enough, as in the masking rule). Every
+position where both show one allele becomes a site with that allele as ALT, and from there on the run is
+a --known_sites run with that table: the pair's own VCF SNV positions are left out, every read base at
+a site that shows its ALT becomes the reference base where its record is decoded, and with
+--masked_base_quality Q its quality becomes Q. With --known_sites as well the two tables are OR-ed. The
+run writes exactly what a run without the option writes on BAMs rewritten that way. The discovered list
+is the donor's germline SNV list: it is never logged or written, the log gives counts only. Limits:
+indels are not discovered; a supplementary record's bases in the primary's soft clip are not masked;
+the pre-pass decodes every record a second time.
 
 Multi-GPU: launch under ``torchrun --nproc-per-node N`` (or set WORLD_SIZE/RANK/LOCAL_RANK):
 contigs are sharded round-robin over the ranks; each rank decodes, masks and writes its own
@@ -86,6 +100,10 @@ def exec_parser(argv=None):
     parser.add_argument("--known_sites", type=str, metavar="PANEL.vcf[.gz]", default=None,
                         help="Population panel: read bases showing a listed one-base ALT at a listed position "
                              "become the reference base where the record is decoded (default: GANON_KNOWN_SITES)")
+    parser.add_argument("--discover_sites", action=BooleanOptionalAction,
+                        help="Mask every SNV allele that a tumor read and a normal read of the pair both show, "
+                             "genome-wide: a pre-pass over both BAMs builds the pair's own site table (default: "
+                             "GANON_DISCOVER_SITES)")
     parser.add_argument("-v", "--verbose", type=int, required=False, default=2, help="Verbosity of logging")
     parser.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     return parser.parse_args(argv)
@@ -127,6 +145,8 @@ def run_anonymizer(argv=None) -> None:
         os.environ["GANON_HASH_READ_NAMES"] = "1" if config.hash_read_names else "0"
     if config.known_sites is not None:
         os.environ["GANON_KNOWN_SITES"] = config.known_sites
+    if config.discover_sites is not None:
+        os.environ["GANON_DISCOVER_SITES"] = "1" if config.discover_sites else "0"
     from . import native
     try:   # (a malformed key ends the run here, before any file is opened)
         if os.environ.get("GANON_HASH_READ_NAMES", "0") == "1" and native.NAME_KEY_ENV in os.environ:

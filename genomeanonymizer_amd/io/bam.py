@@ -61,18 +61,35 @@ class ReadTable:
     """All records of one BAM file, in file order."""
 
     def __init__(self, path: str, threads: int = 8, handle=None, name_key: Optional[bytes] = None,
-                 known_sites=None):
+                 known_sites=None, site_tally=None):
         """Decode the whole file, or take the records of an open ``ganon_bam`` handle (one
         reference sequence from ``BamReader.contig``); the table owns the handle from here on.
         ``name_key`` (--hash_read_names): every name is replaced, as it is decoded, by
         hex(BLAKE2s(name, key, digest_size=16)) (``ganon_bam_open_keyed``); a handle's names are
         whatever its reader decoded. ``known_sites`` (--known_sites; a known_sites.SitesTable, or a
         PairPanel that makes the table of this file's header): the panel mask rewrites the bases as they
-        are decoded (``ganon_bam_open_ex``); ``known_masked`` counts them."""
+        are decoded (``ganon_bam_open_ex``); ``known_masked`` counts them. ``site_tally``
+        (--discover_sites): a pair (discover_sites.HostTally, dataset 0 tumor / 1 normal): the evidence of
+        every record is OR-ed into the tally as it is decoded (``ganon_bam_open_ex2``), before any mask."""
         lib = native.host_lib()
         if handle is None:
             h = C.c_void_p()
-            if known_sites is not None:
+            if site_tally is not None:
+                tally, dataset = site_tally
+                hdr = BamReader(path, threads=1)
+                try:
+                    seq_of = tally.seq_of_tid(hdr.ref_names)
+                    if known_sites is not None:
+                        from ..known_sites import resolve
+                        known_sites = resolve(known_sites, hdr.ref_names)
+                finally:
+                    hdr.close()
+                self.known_sites = known_sites
+                key = bytes(name_key or b"")
+                rc = lib.ganon_bam_open_ex2(os.fsencode(path), int(threads), key, len(key),
+                                            known_sites.handle if known_sites is not None else None, tally.handle,
+                                            int(dataset), native._ptr(seq_of, native._i32p), len(seq_of), C.byref(h))
+            elif known_sites is not None:
                 from ..known_sites import resolve
                 if hasattr(known_sites, "table"):   # (the table goes by sequence id: the header first)
                     hdr = BamReader(path, threads=1)
@@ -294,6 +311,7 @@ class BamReader:
             lib.ganon_bam_reader_set_window(h, int(window))
         self.inflater = None
         self.known_sites = None
+        self.site_tally = None
         self._dev_masked0 = 0
         v = native.BamView()
         lib.ganon_bam_reader_header(h, C.byref(v))
@@ -339,6 +357,22 @@ class BamReader:
                 native.host_lib().ganon_bam_reader_set_region_decoder(
                     self._h, inflater.region_fn, inflater.handle, inflater.min_blocks,
                     C.cast(hl.ganon_pinned_free, C.c_void_p))
+
+    def set_site_tally(self, tally, dataset: int = 0) -> None:
+        """--discover_sites: the records of ``contig`` and ``region`` are tallied into ``tally`` (a
+        discover_sites.HostTally) as dataset 0 (tumor) or 1 (normal) from now on, on the reader's threads
+        (``ganon_bam_reader_set_site_tally``); None turns it off. Region reads a GPU inflater decodes are
+        tallied on its context instead (``GpuInflater.set_site_tally``)."""
+        lib = native.host_lib()
+        if tally is None:
+            lib.ganon_bam_reader_set_site_tally(self._h, None, 0, None, 0)
+            self.site_tally = None
+            return
+        seq_of = tally.seq_of_tid(self.ref_names)
+        if lib.ganon_bam_reader_set_site_tally(self._h, tally.handle, int(dataset), native._ptr(seq_of, native._i32p),
+                                               len(seq_of)) != 0:
+            raise native.GanonError(lib.ganon_host_last_error().decode())
+        self.site_tally = (tally, int(dataset))   # (kept alive: the reader's threads read its genome)
 
     def known_masked(self) -> int:
         """--known_sites: bases rewritten in this reader's tables so far, by its host decodes

@@ -223,6 +223,12 @@ def hip_lib():
     lib.ganon_ctx_set_name_key.argtypes = [_p, C.c_char_p, C.c_int32]
     lib.ganon_ctx_set_known_sites.argtypes = [_p, C.c_int32, _i64p, _i32p, _u8p, C.c_int64, C.c_int32]
     lib.ganon_ctx_known_sites_masked.argtypes = [_p, _i64p]
+    lib.ganon_dtally_create.argtypes = [_p, _u8p, C.c_int64, C.POINTER(_p)]
+    lib.ganon_site_compact_tile.argtypes = []
+    lib.ganon_ctx_set_site_tally.argtypes = [_p, _p, C.c_int32, C.c_int32]
+    lib.ganon_dtally_compact.argtypes = [_p, _p, C.c_void_p, _i64p]
+    lib.ganon_dtally_sites.argtypes = [_p, _p, _i32p, _u8p]
+    lib.ganon_dtally_free.argtypes = [_p, _p]
     lib.ganon_deflate_bound.argtypes = [C.c_int64, C.c_int32]
     lib.ganon_deflate_bound.restype = C.c_int64
     lib.ganon_deflate_bgzf.argtypes = [_p, _u8p, C.c_int64, C.c_int32, _u8p, C.c_int64, _i64p, _i32p]
@@ -263,6 +269,8 @@ EXPORTED_HIP_SYMBOLS = (
     "ganon_inflate", "ganon_inflate_hostcb", "ganon_inflate_device_output",
     "ganon_bam_columns", "ganon_bam_dcols_get", "ganon_bam_dcols_download", "ganon_bam_dcols_free",
     "ganon_ctx_set_name_key", "ganon_ctx_set_known_sites", "ganon_ctx_known_sites_masked",
+    "ganon_site_compact_tile", "ganon_dtally_create", "ganon_ctx_set_site_tally", "ganon_dtally_compact",
+    "ganon_dtally_sites", "ganon_dtally_free",
     "ganon_pinned_alloc", "ganon_pinned_free", "ganon_pinned_stats", "ganon_region_decode",
     "ganon_deflate_bound", "ganon_deflate_bgzf",
 )
@@ -281,6 +289,8 @@ EXPORTED_HOST_SYMBOLS = (
     "ganon_bam_open_keyed", "ganon_names_hash", "ganon_bam_reader_set_name_key",
     "ganon_sites_create", "ganon_sites_destroy", "ganon_bam_open_ex", "ganon_bam_known_sites_masked",
     "ganon_bam_reader_set_known_sites", "ganon_bam_reader_known_sites_masked",
+    "ganon_site_tally_create", "ganon_site_tally_destroy", "ganon_site_tally_bytes", "ganon_site_tally_count",
+    "ganon_site_tally_finish", "ganon_site_tally_release", "ganon_bam_open_ex2", "ganon_bam_reader_set_site_tally",
 )
 
 
@@ -338,6 +348,63 @@ def bam_columns_device(ctx, stream, p: int, n: int, on_host: bool) -> Tuple[Dict
         lib.ganon_bam_dcols_free(ctx, h)
 
 
+def site_compact_tile() -> int:
+    """The positions one workgroup of k_site_compact takes (``ganon_site_compact_tile``)."""
+    return int(hip_lib().ganon_site_compact_tile())
+
+
+class DeviceTally:
+    """--discover_sites: the evidence tally of one reference sequence in device memory (``ganon_dtally``,
+    include/ganon.h) on a GpuInflater's context. ``ref_nt16``: the sequence's upper-cased packed bases
+    ((length + 1) // 2 bytes). ``finish(host_bytes)`` ORs in a host tally's bytes of the same sequence
+    (an address or None), compacts on the device and returns (positions int32, codes uint8); the object is
+    released with it."""
+
+    def __init__(self, inflater: "GpuInflater", ref_nt16: np.ndarray, length: int):
+        self._inf = inflater
+        self._lib = inflater._lib
+        ref = np.ascontiguousarray(ref_nt16, np.uint8)
+        if len(ref) < (int(length) + 1) // 2:
+            raise GanonError("DeviceTally: the packed reference is shorter than the sequence")
+        h = _p()
+        if self._lib.ganon_dtally_create(inflater.handle, _ptr(ref, _u8p), int(length), C.byref(h)) != 0:
+            raise GanonError(self._lib.ganon_last_error(inflater.handle).decode(errors="replace"))
+        self._h = h
+        self.length = int(length)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def finish(self, host_bytes=None) -> Tuple[np.ndarray, np.ndarray]:
+        try:
+            if self._inf.site_tally is self:
+                self._inf.set_site_tally(None)
+            n = C.c_int64(0)
+            if self._lib.ganon_dtally_compact(self._inf.handle, self._h, host_bytes, C.byref(n)) != 0:
+                raise GanonError(self._lib.ganon_last_error(self._inf.handle).decode(errors="replace"))
+            pos, code = np.empty(int(n.value), np.int32), np.empty(int(n.value), np.uint8)
+            if self._lib.ganon_dtally_sites(self._inf.handle, self._h, _ptr(pos, _i32p), _ptr(code, _u8p)) != 0:
+                raise GanonError(self._lib.ganon_last_error(self._inf.handle).decode(errors="replace"))
+            return pos, code
+        finally:
+            self.close()
+
+    def close(self) -> None:
+        if self._h:
+            if self._inf.site_tally is self:
+                self._inf.site_tally = None
+            self._lib.ganon_dtally_free(self._inf.handle, self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            if self._inf._h:
+                self.close()
+        except Exception:
+            pass
+
+
 class GpuInflater:
     """BGZF inflate on the GPU (``ganon_inflate``, include/ganon.h): a device
     context of its own (own stream, own grow-only buffers), used by one thread at a time — the
@@ -359,6 +426,7 @@ class GpuInflater:
         self.region_fn = C.cast(lib.ganon_region_decode, _p)   # the reader's region decoder, same user
         self.name_key: Optional[bytes] = None
         self.known_sites = None
+        self.site_tally = None
 
     @property
     def handle(self):
@@ -401,6 +469,16 @@ class GpuInflater:
         if self._lib.ganon_ctx_known_sites_masked(self._h, C.byref(c)) != 0:
             raise GanonError(self._lib.ganon_last_error(self._h).decode(errors="replace"))
         return int(c.value)
+
+    def set_site_tally(self, tally, dataset: int = 0, tid: int = -1) -> None:
+        """--discover_sites: the context's BAM decoder (``bam_columns``, the region decoder) ORs the
+        evidence of the records of BAM sequence ``tid`` into ``tally`` (a ``DeviceTally`` of this
+        inflater) as dataset 0 (tumor) or 1 (normal) from now on (``ganon_ctx_set_site_tally``:
+        k_bam_site_tally after the scatter); None clears it, and no kernel is added."""
+        h = None if tally is None else tally.handle
+        if self._lib.ganon_ctx_set_site_tally(self._h, h, int(dataset), int(tid)) != 0:
+            raise GanonError(self._lib.ganon_last_error(self._h).decode(errors="replace"))
+        self.site_tally = tally
 
     def kernel_ms(self) -> float:
         """k_inflate's time in the last profiled inflate (HIP events on the context's stream)."""
@@ -1809,6 +1887,20 @@ def host_lib():
     lib.ganon_bam_reader_set_known_sites.argtypes = [_p, _p]
     lib.ganon_bam_reader_known_sites_masked.argtypes = [_p]
     lib.ganon_bam_reader_known_sites_masked.restype = C.c_int64
+    lib.ganon_site_tally_create.argtypes = [C.c_int32, _u8p, _i64p, _i64p, C.POINTER(_p)]
+    lib.ganon_site_tally_destroy.argtypes = [_p]
+    lib.ganon_site_tally_destroy.restype = None
+    lib.ganon_site_tally_bytes.argtypes = [_p, C.c_int32]
+    lib.ganon_site_tally_bytes.restype = C.c_void_p
+    lib.ganon_site_tally_count.argtypes = [_p, C.c_int32]
+    lib.ganon_site_tally_count.restype = C.c_int64
+    lib.ganon_site_tally_finish.argtypes = [_p, C.c_int32, _i32p, _u8p, C.c_int64]
+    lib.ganon_site_tally_finish.restype = C.c_int64
+    lib.ganon_site_tally_release.argtypes = [_p, C.c_int32]
+    lib.ganon_site_tally_release.restype = None
+    lib.ganon_bam_open_ex2.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int32, _p, _p, C.c_int32, _i32p, C.c_int32,
+                                       C.POINTER(_p)]
+    lib.ganon_bam_reader_set_site_tally.argtypes = [_p, _p, C.c_int32, _i32p, C.c_int32]
     lib.ganon_bam_view_get.argtypes = [_p, C.POINTER(BamView)]
     lib.ganon_bam_close.argtypes = [_p]
     lib.ganon_bam_reader_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(_p)]

@@ -68,8 +68,9 @@ def anonymize_genome(windows_in_sample: List[Window], tumor_bam_file: str, norma
         return timing
     t0 = time.time()
     name_key = native.read_name_key_default()   # --hash_read_names (None: off)
-    from .known_sites import pair_default
-    known = pair_default(fasta, windows_in_sample)   # --known_sites (None: off)
+    # --known_sites and / or --discover_sites (None: both off)
+    from .discover_sites import pair_default
+    known = pair_default(fasta, windows_in_sample, tumor_bam_file, normal_bam_file, available_threads, anonymizer)
     tumor = ReadTable(tumor_bam_file, threads=available_threads, name_key=name_key, known_sites=known)
     normal = ReadTable(normal_bam_file, threads=available_threads, name_key=name_key, known_sites=known)
     if known is not None:
@@ -81,7 +82,7 @@ def anonymize_genome(windows_in_sample: List[Window], tumor_bam_file: str, norma
         from .stream import anonymize_genome_streaming
         return anonymize_genome_streaming(windows_in_sample, tumor_bam_file, normal_bam_file, fasta, anonymizer,
                                           tumor_output_fastq, normal_output_fastq, record_statistics,
-                                          available_threads, compress_output=compress_output)
+                                          available_threads, compress_output=compress_output, known=(known,))
     t1 = time.time()
     planner = make_planner(tumor, normal, fasta, windows_in_sample)
     try:
@@ -92,7 +93,7 @@ def anonymize_genome(windows_in_sample: List[Window], tumor_bam_file: str, norma
         from .stream import anonymize_genome_streaming
         return anonymize_genome_streaming(windows_in_sample, tumor_bam_file, normal_bam_file, fasta, anonymizer,
                                           tumor_output_fastq, normal_output_fastq, record_statistics,
-                                          available_threads, compress_output=compress_output)
+                                          available_threads, compress_output=compress_output, known=(known,))
     t2 = time.time()
     res = anonymizer.anonymize(planner, plan)
     t3 = time.time()

@@ -1183,13 +1183,15 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
                                anonymizer: CompleteGermlineAnonymizer, tumor_out: str, normal_out: str,
                                record_statistics: bool, threads: int = 8, dist=None,
                                normal_stats_path: Optional[str] = None, block_size: Optional[int] = None,
-                               window_bytes: int = 0, compress_output: Optional[bool] = None) -> dict:
+                               window_bytes: int = 0, compress_output: Optional[bool] = None,
+                               known: Optional[tuple] = None) -> dict:
     """One tumor/normal pair, contig by contig (single rank when ``dist`` is None, else the
     ranks of the initialised torch.distributed world, each on its own contigs: distributed.py).
     Output files, statistics and errors are the reference's (SR:625-760). ``compress_output``
     (None: GANON_COMPRESS_OUTPUT): the files are ``.fastq.gz``, BGZF members deflated job by job
     into per-rank spools and assembled at the end (_assemble_compressed); their decompressed bytes
-    are the plain run's."""
+    are the plain run's. ``known``: (the pair's PairPanel or None,) where the caller has made it
+    already — the whole-sample path that turns to this one —, else it is made here."""
     from .distributed import Link, assign_contigs
     t_start = time.time()
     comm = _Comm(dist)
@@ -1199,9 +1201,14 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
     compress = native.compress_output_default() if compress_output is None else bool(compress_output)
     # --hash_read_names: one key for every reader of the run, rank 0's on every rank (None: off)
     name_key = native.share_read_name_key(dist)
-    # --known_sites: the panel less this pair's own SNVs, loaded by every rank itself (None: off)
-    from .known_sites import pair_default
-    known = pair_default(fasta, windows)
+    # --known_sites: the panel less this pair's own SNVs, loaded by every rank itself (None: off);
+    # --discover_sites: OR-ed with the sites of the pre-pass over the pair's own BAMs, which runs here,
+    # before any job, the sequences dealt over the ranks (discover_sites.py)
+    prepass: dict = {}
+    if known is None:
+        from .discover_sites import pair_default
+        known = (pair_default(fasta, windows, tumor_bam, normal_bam, threads, anonymizer, dist, window_bytes, prepass),)
+    known = known[0]
     deflater = None
     spools: List[str] = []
     segs: List[Tuple[int, int, int, int]] = []   # (job, file, spool offset, compressed length) of this rank's jobs
@@ -1216,6 +1223,7 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
         block_size = _writer.io_block_size(os.path.dirname(os.path.abspath(tumor_out)))
     timing = {"decode_s": 0.0, "plan_s": 0.0, "mask_s": 0.0, "format_s": 0.0, "prefetch_s": 0.0, "resolve_s": 0.0,
               "write_s": 0.0, "wait_s": 0.0, "writer_wait_s": 0.0, "prunes": 0, "jobs": 0, "reads": 0, "bases": 0}
+    timing.update(prepass)
     failure: Optional[BaseException] = None
     if rank == 0 and not compress:
         for p in paths:

@@ -476,6 +476,28 @@ GANON_API int ganon_ctx_set_name_key(ganon_ctx *ctx, const uint8_t *key, int32_t
 GANON_API int ganon_ctx_set_known_sites(ganon_ctx *ctx, int32_t n_ref, const int64_t *site_off, const int32_t *site_pos,
                                         const uint8_t *site_code, int64_t n, int32_t quality);
 GANON_API int ganon_ctx_known_sites_masked(ganon_ctx *ctx, int64_t *masked);
+/* --discover_sites (additive; the ABI version stays 5). A device site tally is the evidence tally of
+ * include/ganon_host.h (ganon_site_tally_create: the rule, the byte per position) of ONE reference
+ * sequence, in device memory: ganon_dtally_create uploads the sequence's upper-cased nt16 bases
+ * (ref_nt16: (len + 1) / 2 host bytes, base 0 the first byte's high nibble) and makes len zeroed bytes.
+ * ganon_ctx_set_site_tally(ctx, tally, dataset, tid): from now on ganon_bam_columns and
+ * ganon_region_decode on this context run k_bam_site_tally after the scatter, over the columns in
+ * device memory (in a region read: the kept records only), which ORs the evidence of the records of BAM
+ * sequence id `tid` into the tally as dataset 0 (tumor) or 1 (normal); records of other sequences give
+ * none. tally NULL clears it: no kernel is added and the decoder's kernels are those of a context that
+ * never had one. ganon_dtally_compact ORs in host_bytes (len bytes of a host tally of the same
+ * sequence, ganon_site_tally_bytes; NULL: none), intersects (alt = low & high nibble) and writes the
+ * sites in position order in device memory (k_site_compact), *n their number; the tally bytes are
+ * never downloaded. ganon_dtally_sites copies the n positions and codes (ref_nt16 << 4 | alt) to the
+ * host. ganon_dtally_free releases everything (and clears the context's tally if it is this one).
+ * ganon_site_compact_tile: the positions one workgroup of k_site_compact takes. */
+typedef struct ganon_dtally ganon_dtally;
+GANON_API int ganon_site_compact_tile(void);
+GANON_API int ganon_dtally_create(ganon_ctx *ctx, const uint8_t *ref_nt16, int64_t len, ganon_dtally **out);
+GANON_API int ganon_ctx_set_site_tally(ganon_ctx *ctx, ganon_dtally *tally, int32_t dataset, int32_t tid);
+GANON_API int ganon_dtally_compact(ganon_ctx *ctx, ganon_dtally *tally, const uint8_t *host_bytes, int64_t *n);
+GANON_API int ganon_dtally_sites(ganon_ctx *ctx, ganon_dtally *tally, int32_t *pos, uint8_t *code);
+GANON_API int ganon_dtally_free(ganon_ctx *ctx, ganon_dtally *tally);
 
 /* A region read's window decoded on the device: the reader's region decoder (ganon_region_fn of
  * include/ganon_host.h, user = a ganon_ctx; libganon_host.so's ganon_bam_reader_region, the

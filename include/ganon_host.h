@@ -90,6 +90,37 @@ GANON_HOST_API int ganon_bam_open_ex(const char *path, int threads, const uint8_
 /* The bases the panel mask rewrote while this table was decoded on the host (0 for a table a region
  * decoder made: include/ganon.h ganon_ctx_known_sites_masked counts those). */
 GANON_HOST_API int64_t ganon_bam_known_sites_masked(const ganon_bam *bam);
+/* --discover_sites (additive). An evidence tally over the sequences of one run: n_seq sequences of the
+ * upper-cased nt16 genome `nt16` (two bases per byte, a sequence's base 0 at nibble index nib_off[s], in
+ * the high nibble when that index is even; nib_off[s] = -1: the sequence has no reference, nothing on
+ * it is evidence), len[s] bases each. `nt16` is not copied: it must outlive the tally and every reader
+ * it is set on. A decoder with a tally and a dataset (0 tumor, 1 normal) ORs, where a record is
+ * decoded, the evidence of the record into a byte per position (low nibble: tumor alleles, high
+ * nibble: normal alleles; nt16 bit set): every base that is aligned (CIGAR M, = or X from pos; query
+ * index < l_seq) to a position 0 <= r < len[s], is one of A, C, G, T and differs from a reference base
+ * that is one of A, C, G, T. Records with flag & 4, tid < 0, no CIGAR or no bases give none; there is
+ * no other filter. seq_of_tid[tid] is the tally's sequence of a file's BAM sequence id (-1: none). A
+ * sequence's bytes are allocated zeroed with its first evidence. Position r of a sequence is a site when
+ * low & high is non-zero, its code ref_nt16 << 4 | (low & high) (ganon_sites_create's table). The OR
+ * is atomic: readers on several threads may share a tally, records may be tallied in any order and more
+ * than once. The handle may be destroyed while readers made with it live on. No process-global state.
+ * ganon_site_tally_bytes: the sequence's byte array (NULL: no evidence yet), for a device compaction
+ * that ORs it in (include/ganon.h) — then ganon_site_tally_release frees it. ganon_site_tally_count:
+ * the sites of a sequence now. ganon_site_tally_finish: writes them in position order (at most cap;
+ * -1 with an error when they are more) and frees the bytes; returns their number. */
+typedef struct ganon_site_tally ganon_site_tally;
+GANON_HOST_API int ganon_site_tally_create(int32_t n_seq, const uint8_t *nt16, const int64_t *nib_off, const int64_t *len,
+                                           ganon_site_tally **out);
+GANON_HOST_API void ganon_site_tally_destroy(ganon_site_tally *tally);
+GANON_HOST_API const uint8_t *ganon_site_tally_bytes(const ganon_site_tally *tally, int32_t seq);
+GANON_HOST_API int64_t ganon_site_tally_count(const ganon_site_tally *tally, int32_t seq);
+GANON_HOST_API int64_t ganon_site_tally_finish(ganon_site_tally *tally, int32_t seq, int32_t *pos, uint8_t *code, int64_t cap);
+GANON_HOST_API void ganon_site_tally_release(ganon_site_tally *tally, int32_t seq);
+/* ganon_bam_open_ex with a site tally as well (NULL: none; then dataset, seq_of_tid and n_tid are not
+ * read). The tally sees the bases as the file has them, before any known-sites mask. */
+GANON_HOST_API int ganon_bam_open_ex2(const char *path, int threads, const uint8_t *key, int32_t key_len,
+                                      const ganon_sites *sites, const ganon_site_tally *tally, int32_t dataset,
+                                      const int32_t *seq_of_tid, int32_t n_tid, ganon_bam **out);
 GANON_HOST_API int ganon_bam_view_get(ganon_bam *bam, ganon_bam_view *view);
 GANON_HOST_API const char *ganon_bam_error(ganon_bam *bam);
 GANON_HOST_API void ganon_bam_close(ganon_bam *bam);
@@ -155,6 +186,12 @@ GANON_HOST_API int ganon_bam_reader_set_name_key(ganon_bam_reader *reader, const
  * turns it off. ganon_bam_reader_known_sites_masked: the bases this reader's host decodes rewrote. */
 GANON_HOST_API int ganon_bam_reader_set_known_sites(ganon_bam_reader *reader, const ganon_sites *sites);
 GANON_HOST_API int64_t ganon_bam_reader_known_sites_masked(const ganon_bam_reader *reader);
+/* --discover_sites: the records of ganon_bam_reader_contig and ganon_bam_reader_region are tallied
+ * from now on, inside the column pass on the reader's threads — the host path of a region read too
+ * (a region decoder tallies on its context: ganon_ctx_set_site_tally). n_tid is the header's sequence
+ * count. NULL turns it off. */
+GANON_HOST_API int ganon_bam_reader_set_site_tally(ganon_bam_reader *reader, const ganon_site_tally *tally, int32_t dataset,
+                                                   const int32_t *seq_of_tid, int32_t n_tid);
 GANON_HOST_API int ganon_bam_reader_header(ganon_bam_reader *reader, ganon_bam_view *view);
 GANON_HOST_API int ganon_bam_reader_contig(ganon_bam_reader *reader, int32_t tid, ganon_bam **out);
 /* The records of tid overlapping [beg, end) (0-based; htslib's region semantics: pos < end and

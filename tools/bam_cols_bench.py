@@ -17,6 +17,12 @@ record, and the host decoder hashes inside its column pass.
 positions per 1,000 bases of each sequence, REF the FASTA's base, one random ALT): k_bam_known_mask joins
 the kernel list, the host decoder masks inside its column pass, and the line reports the sites and the
 bases rewritten.
+
+--site_tally: the same with an evidence tally on both sides (--discover_sites): a device tally of the
+sequence most records lie on, as the tumor dataset — k_bam_site_tally joins the kernel list —, the host
+decoder tallying inside its column pass; the line reports the positions with evidence on both sides (they
+must agree), k_site_compact over that sequence and over a synthetic 20 Mb sequence whose bytes come up
+from the host (one position in a thousand a site).
 """
 import argparse
 import json
@@ -62,7 +68,28 @@ def synthetic_panel(ref_path: str, ref_names, per_kb: float, seed: int = 1):
     return SitesTable(np.array(off, np.int64), np.concatenate(pos), np.concatenate(code))
 
 
-def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = None, sites_per_kb: float = 0.0) -> dict:
+def compact_20mb(g, n: int = 20_000_000, seed: int = 2) -> dict:
+    """k_site_compact on a synthetic ``n``-base sequence: the evidence bytes uploaded as a host tally's."""
+    from genomeanonymizer_amd import native
+    rng = np.random.default_rng(seed)
+    ref = rng.integers(0, 4, n).astype(np.uint8)
+    packed = ((np.uint8(1) << ref[0::2]) << 4 | (np.uint8(1) << ref[1::2])).astype(np.uint8)
+    host = np.zeros(n, np.uint8)
+    at = rng.choice(n, n // 1000, replace=False)
+    alt = (np.uint8(1) << ((ref[at] + 1) % 4)).astype(np.uint8)
+    host[at] = alt | (alt << 4)
+    host[rng.choice(n, n // 100, replace=False)] |= 0x10      # evidence on one side alone
+    dt = native.DeviceTally(g, packed, n)
+    pos, code = dt.finish(host.ctypes.data)
+    per = dict(g.kernel_times())
+    exp = np.nonzero(host & (host >> 4) & 15)[0]
+    return {"bases": n, "sites": int(len(pos)), "kernels_ms": {k: round(v, 3) for k, v in per.items()},
+            "equals_numpy": bool(np.array_equal(pos, exp) and np.array_equal(code & 15, (host & (host >> 4) & 15)[exp])
+                                 and np.array_equal(code >> 4, np.uint8(1) << ref[exp]))}
+
+
+def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = None, sites_per_kb: float = 0.0,
+            site_tally: bool = False) -> dict:
     import gzip
     from genomeanonymizer_amd import native
     from genomeanonymizer_amd.io.bam import ReadTable
@@ -87,6 +114,20 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
             table = synthetic_panel(paths["ref"], hdr.ref_names, sites_per_kb)
             hdr.close()
         g.set_known_sites(table)
+        tally = dtally = None
+        tally_tid = -1
+        if site_tally:
+            from genomeanonymizer_amd.discover_sites import HostTally
+            from genomeanonymizer_amd.io.bam import BamReader
+            from genomeanonymizer_amd.io.fasta import FastaRef
+            hdr = BamReader(paths["T"], 1)
+            tally = HostTally.of_fasta(FastaRef(paths["ref"]))
+            seq_of = tally.seq_of_tid(hdr.ref_names)
+            hdr.close()
+            tally_tid = int(np.frombuffer(recs[4:8], np.int32)[0])   # (the first record's sequence)
+            seq = int(seq_of[tally_tid])
+            dtally = native.DeviceTally(g, tally.reference_of(seq), int(tally.lengths[seq]))
+            g.set_site_tally(dtally, 0, tally_tid)
         runs = []
         cols, _ = native.bam_columns_device(g.handle, stream, p, len(stream), on_host=True)   # (warm: blocks cached)
         for _ in range(reps):
@@ -101,6 +142,14 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
                 per[name] = per.get(name, 0.0) + float(arr[i].ms)
             runs.append((sum(per.values()), per, wall, fixes))
         dev_masked = g.known_sites_masked() // (reps + 1) if table is not None else 0
+        tally_out = None
+        if site_tally:
+            # the tumor evidence again as the normal dataset: every position with evidence is a site
+            g.set_site_tally(dtally, 1, tally_tid)
+            native.bam_columns_device(g.handle, stream, p, len(stream), on_host=True)
+            dpos, dcode = dtally.finish()
+            tally_out = {"tid": tally_tid, "sequence_bases": int(tally.lengths[seq]), "positions_with_evidence_device": int(len(dpos)),
+                         "compact_kernels_ms": {k: round(v, 3) for k, v in g.kernel_times()}, "compact_20Mb": compact_20mb(g)}
         g.close()
         best = min(runs, key=lambda x: x[0])
         nr = len(cols["pos"])
@@ -110,8 +159,14 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
         t = None
         for th in (1, threads):
             t0 = time.perf_counter()
-            t = ReadTable(path, threads=th, name_key=name_key, known_sites=table)
+            t = ReadTable(path, threads=th, name_key=name_key, known_sites=table,
+                          site_tally=(tally, 0) if site_tally else None)
             host[th] = time.perf_counter() - t0
+        if site_tally:
+            ReadTable(path, threads=threads, site_tally=(tally, 1))
+            hpos, hcode = tally.finish(seq)
+            tally_out["positions_with_evidence_host"] = int(len(hpos))
+            tally_out["device_equals_host"] = bool(np.array_equal(hpos, dpos) and np.array_equal(hcode, dcode))
         equal = len(cols["pos"]) == t.n and all(np.array_equal(cols[f], getattr(t, f)) for f in COLS + BLOBS)
         out_bytes = sum(cols[f].nbytes for f in COLS + BLOBS) + cols["rec_off"].nbytes
         alg = (len(stream) - p) + out_bytes   # the records read once, the columns written once
@@ -130,6 +185,7 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
             "known_sites": None if table is None else {
                 "sites_per_kb": sites_per_kb, "sites": table.n, "table_bytes": int(5 * table.n + 8 * (table.n_ref + 1)),
                 "bases_rewritten_device": int(dev_masked), "bases_rewritten_host": int(t.known_masked)},
+            "site_tally": tally_out,
             "workload": f"configs[0] tumor BAM records tiled x{tiles} ({nr} records, 150 bp); device: the stream "
                         f"resident in HBM, kernels only (HIP events on the context's stream); call wall adds the H2D "
                         f"copy, the scans' host reads and the D2H of the columns; host: ganon_bam_open of the same "
@@ -148,13 +204,15 @@ def main() -> None:
                     help="decode with a read-name key (GANON_READ_NAME_KEY as hex, else a fixed benchmark key)")
     ap.add_argument("--known_sites", type=float, default=0.0, metavar="SITES_PER_KB",
                     help="decode with a synthetic panel of this many sites per 1,000 bases (both sides)")
+    ap.add_argument("--site_tally", action="store_true",
+                    help="decode with an evidence tally (--discover_sites) on both sides, and time k_site_compact")
     args = ap.parse_args()
     key = None
     if args.hash_names:
         from genomeanonymizer_amd import native
         v = os.environ.get(native.NAME_KEY_ENV)
         key = native.parse_name_key(v) if v is not None else BENCH_KEY
-    print(json.dumps(measure(args.mb, args.threads, args.reps, key, args.known_sites)))
+    print(json.dumps(measure(args.mb, args.threads, args.reps, key, args.known_sites, args.site_tally)))
 
 
 if __name__ == "__main__":

@@ -25,6 +25,8 @@ Prints one JSON line with per-stage seconds, reads/s, bases/s and the process's 
                              # §4h): the same line with "hash_read_names": true
     GANON_KNOWN_SITES=PANEL.vcf[.gz]  # --known_sites: panel SNVs masked at decode: the same line
                              # with "known_sites": the path
+    GANON_DISCOVER_SITES=1   # --discover_sites: the pair's own shared SNV alleles masked: the same
+                             # line with "discover_sites": true and the pre-pass's sites and seconds
     E2E_DISK_PROBE=1 ...     # also time 2 GiB of pwrite into OUTDIR (4 files at once, as the product
                              # writes; page cache, then with fsync): the box's write bandwidth
 """
@@ -220,6 +222,7 @@ def main():
                      "masked_base_quality": _native.masked_base_quality_default(),
                      "hash_read_names": _native.read_name_key_default() is not None,
                      "known_sites": os.environ.get("GANON_KNOWN_SITES") or None,
+                     "discover_sites": os.environ.get("GANON_DISCOVER_SITES", "0") == "1",
                      "cpus_available": len(os.sched_getaffinity(0)),
                      "output_bytes": sum(os.path.getsize(os.path.join(out, f"{x}_{mode}{s}{gz}"))
                                          for x in ("tumor", "normal") for s in (".1.fastq", ".2.fastq"))}

@@ -1074,6 +1074,16 @@ GANON_API int ganon_bam_columns(ganon_ctx *ctx, const uint8_t *stream, int64_t p
   return GANON_OK;
 }
 
+GANON_API int ganon_bam_walk_params(int64_t out[5]) {
+  if (!out) return GANON_E_ARG;
+  out[0] = kChunk;
+  out[1] = kProbe;
+  out[2] = kGuessSpan;
+  out[3] = kStage;
+  out[4] = kScatRecs;
+  return GANON_OK;
+}
+
 GANON_API int ganon_ctx_set_name_key(ganon_ctx *ctx, const uint8_t *key, int32_t key_len) {
   if (!ctx) return GANON_E_ARG;
   if (key_len < 0 || key_len > ganon_nh::kMaxKey || (key_len > 0 && !key))

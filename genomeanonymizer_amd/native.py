@@ -220,6 +220,7 @@ def hip_lib():
     lib.ganon_bam_dcols_get.argtypes = [_p, C.POINTER(BamCols), _i64p]
     lib.ganon_bam_dcols_download.argtypes = [_p, _p, C.POINTER(BamCols)]
     lib.ganon_bam_dcols_free.argtypes = [_p, _p]
+    lib.ganon_bam_walk_params.argtypes = [_i64p]
     lib.ganon_ctx_set_name_key.argtypes = [_p, C.c_char_p, C.c_int32]
     lib.ganon_ctx_set_known_sites.argtypes = [_p, C.c_int32, _i64p, _i32p, _u8p, C.c_int64, C.c_int32]
     lib.ganon_ctx_known_sites_masked.argtypes = [_p, _i64p]
@@ -268,7 +269,7 @@ EXPORTED_HIP_SYMBOLS = (
     "ganon_indel_upload", "ganon_indel_run", "ganon_indel_download", "ganon_indel_info", "ganon_indel_free",
     "ganon_inflate", "ganon_inflate_hostcb", "ganon_inflate_device_output",
     "ganon_bam_columns", "ganon_bam_dcols_get", "ganon_bam_dcols_download", "ganon_bam_dcols_free",
-    "ganon_ctx_set_name_key", "ganon_ctx_set_known_sites", "ganon_ctx_known_sites_masked",
+    "ganon_bam_walk_params", "ganon_ctx_set_name_key", "ganon_ctx_set_known_sites", "ganon_ctx_known_sites_masked",
     "ganon_site_compact_tile", "ganon_dtally_create", "ganon_ctx_set_site_tally", "ganon_dtally_compact",
     "ganon_dtally_sites", "ganon_dtally_free",
     "ganon_pinned_alloc", "ganon_pinned_free", "ganon_pinned_stats", "ganon_region_decode",
@@ -346,6 +347,18 @@ def bam_columns_device(ctx, stream, p: int, n: int, on_host: bool) -> Tuple[Dict
         return cols, int(fixes.value)
     finally:
         lib.ganon_bam_dcols_free(ctx, h)
+
+
+BAM_WALK_PARAMS = ("chunk", "probe", "guess_span", "scat_stage", "scat_recs")
+
+
+def bam_walk_params() -> Dict[str, int]:
+    """The record walk's compile-time constants (``ganon_bam_walk_params``): kChunk, kProbe, kGuessSpan,
+    GANON_SCAT_STAGE and GANON_SCAT_RECS of csrc/ganon_bam.hip, under the names of BAM_WALK_PARAMS."""
+    out = np.zeros(5, np.int64)
+    if hip_lib().ganon_bam_walk_params(_ptr(out, _i64p)) != 0:
+        raise GanonError("ganon_bam_walk_params failed")
+    return dict(zip(BAM_WALK_PARAMS, (int(v) for v in out)))
 
 
 def site_compact_tile() -> int:

@@ -455,6 +455,11 @@ GANON_API int ganon_bam_dcols_get(const ganon_bam_dcols *c, ganon_bam_cols *devi
 GANON_API int ganon_bam_dcols_download(ganon_ctx *ctx, const ganon_bam_dcols *c, const ganon_bam_cols *host);
 /* (with the context that made it: its device blocks return to that context's cache) */
 GANON_API int ganon_bam_dcols_free(ganon_ctx *ctx, ganon_bam_dcols *c);
+/* The record walk's compile-time constants (additive; the ABI version stays 5), for tests that build
+ * streams on their edges: out[0] the chunk bytes (kChunk), out[1] the chained records that make a guess
+ * (kProbe), out[2] the guess window in bytes from a chunk's start (kGuessSpan), out[3] the LDS bytes the
+ * scatter stages per workgroup (GANON_SCAT_STAGE), out[4] its records per workgroup (GANON_SCAT_RECS). */
+GANON_API int ganon_bam_walk_params(int64_t out[5]);
 /* --hash_read_names (additive; the ABI version stays 5). ganon_ctx_set_name_key(ctx, key, 1..32): from
  * now on ganon_bam_columns and ganon_region_decode on this context return every record's name
  * replaced by hex(BLAKE2s(name, key, digest_size = 16)), 32 lowercase hex characters (RFC 7693 keyed

@@ -24,6 +24,12 @@ def parse(path):
     (packed bytes), ``qual`` and ``aux`` (bytes)."""
     with open(path, "rb") as fh:
         d = gzip.decompress(fh.read())
+    return parse_stream(d, header_end(d))
+
+
+def header_end(d) -> int:
+    """The offset of the first record of the inflated stream ``d``: after the header text and the
+    reference sequence list (SAM/BAM v1 §4.2)."""
     assert d[:4] == b"BAM\x01"
     l_text, = struct.unpack_from("<i", d, 4)
     p = 8 + l_text
@@ -32,6 +38,12 @@ def parse(path):
     for _ in range(n_ref):
         l_name, = struct.unpack_from("<i", d, p)
         p += 4 + l_name + 4
+    return p
+
+
+def parse_stream(d, p):
+    """``parse`` on an inflated stream: the records that lie back to back in ``d`` from offset ``p`` to
+    its end."""
     out = []
     while p < len(d):
         block_size, = struct.unpack_from("<i", d, p)

@@ -8,6 +8,11 @@ same file: synthetic scenarios (short and long reads), the stream left on the de
 inflate, and hand-made streams built to defeat the chunk guesses (records longer than a chunk,
 copies of whole record chains inside aux bytes, names without their NUL, unmapped records), plus
 the host decoder's errors.
+
+The walk's edges — the chunk grid, the stream's last bytes, the scatter's LDS stage, the per-record
+arithmetic, decoys, `fixes` by equality — are pinned by the hand-built streams of tests/bam_streams.py
+against the specification's restatement: tests/test_bam_streams.py (CPU) and
+tests/test_gpu_bam_streams.py (device).
 """
 import gzip
 import struct
@@ -38,29 +43,7 @@ def assert_same(cols, t):
         assert np.array_equal(cols[f], getattr(t, f)), f
 
 
-def _header(contigs) -> bytes:
-    text = "@HD\tVN:1.6\n" + "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in contigs)
-    h = b"BAM\x01" + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", len(contigs))
-    for n, l in contigs:
-        nb = n.encode() + b"\x00"
-        h += struct.pack("<i", len(nb)) + nb + struct.pack("<i", l)
-    return h
-
-
-def _record(rng, i: int, aux: bytes = b"", l_seq: int = None, nul: bool = True, flag: int = None) -> bytes:
-    name = f"q{i}".encode() + (b"\x00" if nul else b"")
-    l_seq = int(rng.integers(0, 300)) if l_seq is None else l_seq
-    ops = []
-    for _ in range(int(rng.integers(0, 6))):
-        ops.append((int(rng.integers(1, 80)) << 4) | int(rng.choice([0, 1, 2, 3, 4, 7, 8])))
-    flag = int(rng.choice([0, 1 | 2 | 64, 1 | 16 | 128, 4, 1 | 4 | 8])) if flag is None else flag
-    body = struct.pack("<iiBBHHHiiii", int(rng.integers(-1, 3)), int(rng.integers(-1, 10**6)), len(name),
-                       int(rng.integers(0, 61)), 4680, len(ops), flag, l_seq, int(rng.integers(-1, 3)),
-                       int(rng.integers(-1, 10**6)), int(rng.integers(-500, 500)))
-    body += name + struct.pack(f"<{len(ops)}I", *ops)
-    body += rng.integers(0, 256, (l_seq + 1) // 2, dtype=np.uint8).tobytes()
-    body += rng.integers(0, 60, l_seq, dtype=np.uint8).tobytes() + aux
-    return struct.pack("<i", len(body)) + body
+from bam_streams import _header, _record  # noqa: E402,F401  (the builders' home; namehash_helpers imports them from here)
 
 
 def adversarial_stream(seed: int = 5, n: int = 3000) -> bytes:
@@ -244,7 +227,11 @@ def _walk_chunks(d: bytes, p: int, chunk: int, probe: int = 4, span: int = None)
         ce = min(n, p + (c + 1) * chunk)
         s = e
         while 0 <= s < ce:
-            s += 4 + i32(s)
+            bs = i32(s) if s + 4 <= n else -1
+            if bs < 32 or s + 4 + bs > n:   # (the device walk stops on a bad size: exit -2)
+                s = -2
+                break
+            s += 4 + bs
         entry[c], exitp[c] = e, (s if e >= 0 else -1)
 
     for c in range(nc):

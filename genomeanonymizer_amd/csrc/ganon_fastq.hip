@@ -1517,9 +1517,12 @@ GANON_API int ganon_fastq_upload(ganon_ctx *ctx, const ganon_fastq_records *in, 
     for (int64_t i = a; i < b; ++i) {
       const int s = in->seq_sel[i], q = in->qual_sel[i];
       FqRec &R = rec[i];
-      R.seq = (uint64_t)(in->seq_nib_off[i] - 2 * seq_base[s]) | ((uint64_t)s << 56) |
+      // an empty field uses no source byte and does not count toward its buffer's extent: its offset
+      // may lie below the slice (a negative difference would spill into the flag bits), so it is dropped
+      R.seq = (uint64_t)(in->seq_len[i] ? in->seq_nib_off[i] - 2 * seq_base[s] : 0) | ((uint64_t)s << 56) |
               ((uint64_t)(in->reverse[i] != 0) << 58) | ((uint64_t)(in->qual_rev[i] != 0) << 59);
-      R.qual = (uint64_t)(in->qual_off[i] - qe[q].lo) | ((uint64_t)in->mate[i] << 48) | ((uint64_t)q << 56);
+      R.qual = (uint64_t)(in->qual_len[i] ? in->qual_off[i] - qe[q].lo : 0) | ((uint64_t)in->mate[i] << 48) |
+               ((uint64_t)q << 56);
       R.name = (uint64_t)(in->name_len[i] ? in->name_off[i] - ne.lo : 0) | ((uint64_t)in->name_len[i] << 48);
       R.len = (uint32_t)in->seq_len[i];
       R.qlen = (uint32_t)in->qual_len[i];

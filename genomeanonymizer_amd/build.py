@@ -53,7 +53,7 @@ def build_hip(force: bool = False) -> str:
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
     hdrs = [os.path.join(REPO, "include", "ganon.h"), os.path.join(CSRC, "ganon_ctx.h"), os.path.join(CSRC, "ganon_batch.h"),
             os.path.join(CSRC, "ganon_deflate_core.h"), os.path.join(CSRC, "ganon_name_hash.h"),
-            os.path.join(CSRC, "ganon_known_sites.h"),
+            os.path.join(CSRC, "ganon_known_sites.h"), os.path.join(CSRC, "ganon_sa_clips.h"),
             os.path.join(CSRC, "ganon_site_tally.h"), __file__]
     if not (force or _stale(HIP_LIB, srcs + hdrs)):
         return HIP_LIB
@@ -93,6 +93,7 @@ def build_host(force: bool = False) -> str:
     hdr = os.path.join(REPO, "include", "ganon_host.h")
     if force or _stale(HOST_LIB, srcs + [hdr, os.path.join(CSRC, "ganon_name_hash.h"),
                                        os.path.join(CSRC, "ganon_known_sites.h"),
+                                       os.path.join(CSRC, "ganon_sa_clips.h"),
                                        os.path.join(CSRC, "ganon_site_tally.h"), __file__]):
         tmp = f"{HOST_LIB}.{os.getpid()}.tmp"
         _run(["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-pthread",

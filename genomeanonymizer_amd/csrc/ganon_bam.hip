@@ -40,6 +40,12 @@
 // rule). A thread per record — almost all leave after one lower bound —, a wave per record with more
 // than 48 CIGAR ops. Without a table nothing of this runs.
 //
+// SA clips (--mask_sa_clips, ganon_ctx_set_sa_clips). With the header's names on the context as well
+// k_bam_sa_clips runs right after k_bam_known_mask: the soft-clipped bases of a record with an SA:Z tag
+// are masked along the alignments the tag names (ganon_sa_clips.h, the host decoder's rule). A thread
+// per record — almost all leave after their first and last CIGAR word —, the candidates compacted
+// through LDS and taken a thread each. Without the names nothing of this runs.
+//
 // Site discovery (--discover_sites, ganon_ctx_set_site_tally). With a device tally on the context
 // k_bam_site_tally runs after the scatter over the columns in device memory: the alleles the records of
 // one reference sequence show against the reference are OR-ed into a byte per position
@@ -619,6 +625,73 @@ __global__ void __launch_bounds__(kBamThreads) k_bam_known_mask(ganon_bam_cols V
   if (threadIdx.x == 0 && s_cnt) atomicAdd(count, (unsigned long long)s_cnt);
 }
 
+// The SA clip mask of --mask_sa_clips over the decoded columns, after k_bam_known_mask in stream order
+// (ganon_sa_clips.h has the rule; a byte that holds an aligned and a clipped nibble is written by the
+// one kernel, then by the other). A thread per record loads flag, n_cigar, cig_off and its first and
+// last CIGAR word (24 bytes) and leaves unless one of them is S or H: nearly every record. The rest
+// settle their clips (ganon_sa::own_clip) and scan their aux bytes for the SA:Z value; those that have
+// one are listed in LDS with the value's bounds and, after the barrier, taken by the block's first
+// threads, a thread per candidate: the tag is tens of bytes of decimal text that only a serial parse
+// reads, and an M run holds a few sites at most, so a wave per candidate would idle 63 lanes, while
+// the compaction packs a block's few candidates into one wave instead of leaving each to diverge in
+// its own. One thread owns a record, whose bases are whole bytes of its own: plain byte stores. Counts:
+// a shuffle sum and one LDS add per wave, one global add per count per workgroup that has any.
+__global__ void __launch_bounds__(kBamThreads) k_bam_sa_clips(ganon_bam_cols V, int64_t nr, ganon_ks::View S,
+                                                              ganon_sa::Names N, unsigned long long *__restrict__ count) {
+  __shared__ int s_cand[kBamThreads], s_v0[kBamThreads], s_v1[kBamThreads];
+  __shared__ int s_ncand, s_cnt, s_ign;
+  if (threadIdx.x == 0) s_ncand = s_cnt = s_ign = 0;
+  __syncthreads();
+  const int64_t i0 = (int64_t)blockIdx.x * kBamThreads;
+  const int64_t i = i0 + threadIdx.x;
+  if (i < nr) {
+    const int32_t flag = V.flag[i], ncig = V.n_cigar[i];
+    if (!(flag & 4) && ncig > 0) {
+      const uint32_t *cg = V.cigar + V.cig_off[i];
+      const uint32_t o0 = cg[0] & 15u, o1 = cg[ncig - 1] & 15u;
+      if (o0 == 4u || o0 == 5u || o1 == 4u || o1 == 5u) {
+        const int32_t tid = V.tid[i], lseq = V.l_seq[i], alen = V.aux_len[i];
+        ganon_sa::Clip c;
+        int64_t v0, v1;
+        if (!ganon_ks::skips(S, tid, (uint32_t)flag, ncig, lseq) && alen > 3 && ganon_sa::own_clip(ncig, lseq, cg, &c) &&
+            ganon_sa::find_sa(V.aux + V.aux_off[i], alen, &v0, &v1)) {
+          const int k = atomicAdd(&s_ncand, 1);
+          s_cand[k] = (int)threadIdx.x;
+          s_v0[k] = (int)v0;
+          s_v1[k] = (int)v1;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int ncand = s_ncand, lane = threadIdx.x & 63;
+  int cnt = 0, ign = 0;
+  if ((int)threadIdx.x < ncand) {
+    const int64_t g = i0 + s_cand[threadIdx.x];
+    const int32_t ncig = V.n_cigar[g], lseq = V.l_seq[g];
+    const uint32_t *cg = V.cigar + V.cig_off[g];
+    ganon_sa::Clip c;
+    ganon_sa::own_clip(ncig, lseq, cg, &c);
+    cnt = ganon_sa::mask_tag(S, N, c, (uint32_t)V.flag[g], lseq, V.seq + V.seq_off[g], V.qual + V.qual_off[g],
+                             V.aux + V.aux_off[g], s_v0[threadIdx.x], s_v1[threadIdx.x], &ign);
+  }
+  if (__any(cnt != 0 || ign != 0)) {
+    for (int s = 32; s > 0; s >>= 1) {
+      cnt += __shfl_xor(cnt, s);
+      ign += __shfl_xor(ign, s);
+    }
+    if (lane == 0) {
+      if (cnt) atomicAdd(&s_cnt, cnt);
+      if (ign) atomicAdd(&s_ign, ign);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_cnt) atomicAdd(count, (unsigned long long)s_cnt);
+    if (s_ign) atomicAdd(count + 1, (unsigned long long)s_ign);
+  }
+}
+
 // ---- --discover_sites: the evidence tally and its compaction ---------------------------------------------
 
 struct StView {
@@ -1010,6 +1083,14 @@ int columns(ganon_ctx *ctx, const uint8_t *d, int64_t p, int64_t n, ganon_bam_dc
     }
     if ((rc = check_launch(ctx, "k_bam_known_mask"))) return rc;
   }
+  if (nr && ctx->ks_block && ctx->sa_block) {   // --mask_sa_clips: the clips of the columns just masked
+    {
+      ganon_detail::KernelScope ks(ctx, "k_bam_sa_clips");
+      hipLaunchKernelGGL(k_bam_sa_clips, dim3(grid_of(nr)), dim3(kBamThreads), 0, s, V, nr, ctx->ks_view, ctx->sa_names,
+                         ctx->sa_count);
+    }
+    if ((rc = check_launch(ctx, "k_bam_sa_clips"))) return rc;
+  }
   if (nr && ctx->st_tally) {   // --discover_sites: the evidence of the columns just written
     const ganon_dtally *D = ctx->st_tally;
     const StView T{D->ref, D->words, D->len, ctx->st_tid, ctx->st_dataset};
@@ -1163,6 +1244,87 @@ GANON_API int ganon_ctx_known_sites_masked(ganon_ctx *ctx, int64_t *masked) {
   if (!ctx || !masked) return fail(ctx, GANON_E_ARG, "ganon_ctx_known_sites_masked: bad arguments");
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
   return ks_collect(ctx, masked);
+}
+
+// The running counts of the names in place, added to sa_total; the device counters are left as they are.
+static int sa_collect(ganon_ctx *ctx, int64_t sum[2]) {
+  sum[0] = ctx->sa_total[0];
+  sum[1] = ctx->sa_total[1];
+  if (!ctx->sa_block) return GANON_OK;
+  unsigned long long c[2] = {0, 0};
+  HIP_OR_FAIL(ganon_detail::readback(c, ctx->sa_count, 16, ctx->stream));
+  HIP_OR_FAIL(ganon_detail::sync_stream(ctx->stream));
+  sum[0] += (int64_t)c[0];
+  sum[1] += (int64_t)c[1];
+  return GANON_OK;
+}
+
+GANON_API int ganon_ctx_set_sa_clips(ganon_ctx *ctx, int32_t n_names, const char *names, const int64_t *name_off,
+                                     const int32_t *name_tid) {
+  if (!ctx) return GANON_E_ARG;
+  if (n_names < 0 || (n_names > 0 && (!names || !name_off || !name_tid)))
+    return fail(ctx, GANON_E_ARG, "ganon_ctx_set_sa_clips: bad arguments");
+  if (n_names > 0) {   // (the kernel trusts the names: what ganon_sites_set_sa_clips checks)
+    if (name_off[0] != 0) return fail(ctx, GANON_E_ARG, "ganon_ctx_set_sa_clips: name_off[0] must be 0");
+    for (int32_t i = 0; i < n_names; ++i) {
+      if (name_off[i + 1] < name_off[i] || name_tid[i] < 0)
+        return fail(ctx, GANON_E_ARG, "ganon_ctx_set_sa_clips: name_off must not decrease, sequence ids >= 0");
+      if (i > 0) {
+        const int64_t la = name_off[i] - name_off[i - 1], lb = name_off[i + 1] - name_off[i];
+        const int c = std::memcmp(names + name_off[i - 1], names + name_off[i], (size_t)std::min(la, lb));
+        if (c > 0 || (c == 0 && la >= lb))
+          return fail(ctx, GANON_E_ARG, "ganon_ctx_set_sa_clips: the names must be sorted bytewise and distinct");
+      }
+    }
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
+  if (ctx->sa_block) {   // the names in place go: their counts stay in the totals
+    int64_t sum[2];
+    const int rc = sa_collect(ctx, sum);
+    if (rc) return rc;
+    ctx->sa_total[0] = sum[0];
+    ctx->sa_total[1] = sum[1];
+    HIP_OR_FAIL(hipFree(ctx->sa_block));   // (waits for the device: no kernel reads it any more)
+    ctx->sa_block = nullptr;
+    ctx->sa_count = nullptr;
+    ctx->sa_names = ganon_sa::Names{};
+  }
+  if (n_names == 0) return GANON_OK;
+  const int64_t nb = name_off[n_names];
+  const int64_t b_off = ((int64_t)(n_names + 1) * 8 + 255) / 256 * 256, b_tid = ((int64_t)n_names * 4 + 255) / 256 * 256,
+                b_blob = (nb + 255) / 256 * 256;
+  void *blk = nullptr;
+  HIP_OR_FAIL(hipMalloc(&blk, (size_t)(b_off + b_tid + b_blob + 256)));
+  uint8_t *at = static_cast<uint8_t *>(blk);
+  hipStream_t s = ctx->stream;
+  const unsigned long long zero[2] = {0, 0};
+  if (hipMemcpyAsync(at, name_off, (size_t)(n_names + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(at + b_off, name_tid, (size_t)n_names * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+      (nb > 0 && hipMemcpyAsync(at + b_off + b_tid, names, (size_t)nb, hipMemcpyHostToDevice, s) != hipSuccess) ||
+      hipMemcpyAsync(at + b_off + b_tid + b_blob, zero, 16, hipMemcpyHostToDevice, s) != hipSuccess ||
+      ganon_detail::sync_stream(s) != hipSuccess) {
+    ganon_detail::sync_stream(s);
+    hipFree(blk);
+    return fail(ctx, GANON_E_DEVICE, "ganon_ctx_set_sa_clips: upload failed");
+  }
+  ctx->sa_block = blk;
+  ctx->sa_names.n = n_names;
+  ctx->sa_names.off = reinterpret_cast<const int64_t *>(at);
+  ctx->sa_names.tid = reinterpret_cast<const int32_t *>(at + b_off);
+  ctx->sa_names.blob = reinterpret_cast<const char *>(at + b_off + b_tid);
+  ctx->sa_count = reinterpret_cast<unsigned long long *>(at + b_off + b_tid + b_blob);
+  return GANON_OK;
+}
+
+GANON_API int ganon_ctx_sa_clips_counts(ganon_ctx *ctx, int64_t *masked, int64_t *ignored) {
+  if (!ctx || !masked || !ignored) return fail(ctx, GANON_E_ARG, "ganon_ctx_sa_clips_counts: bad arguments");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
+  int64_t sum[2];
+  const int rc = sa_collect(ctx, sum);
+  if (rc) return rc;
+  *masked = sum[0];
+  *ignored = sum[1];
+  return GANON_OK;
 }
 
 GANON_API int ganon_site_compact_tile(void) { return kSiteTile; }

@@ -19,6 +19,7 @@
 #include "../../include/ganon.h"
 #include "ganon_name_hash.h"
 #include "ganon_known_sites.h"
+#include "ganon_sa_clips.h"
 #include "ganon_site_tally.h"
 
 struct ganon_dtally;                               // ganon_bam.hip: a device site tally
@@ -79,6 +80,12 @@ struct ganon_ctx {
   ganon_ks::View ks_view{};
   unsigned long long *ks_count = nullptr;   // (device) bases rewritten since the table was set
   int64_t ks_total = 0;                     // ... and by the tables this context held before
+  // ganon_ctx_set_sa_clips (--mask_sa_clips): the header's sorted names in device memory (one block:
+  // off, tid, blob, two counts) and the view k_bam_sa_clips takes; sa_block == nullptr: off, no kernel
+  void *sa_block = nullptr;
+  ganon_sa::Names sa_names{};
+  unsigned long long *sa_count = nullptr;   // (device) [0] clip bases rewritten, [1] entries ignored, since set
+  int64_t sa_total[2] = {0, 0};             // ... and under the names this context held before
   // ganon_ctx_set_site_tally (--discover_sites): the tally k_bam_site_tally ORs the decoded records of
   // BAM sequence st_tid into, as dataset st_dataset; nullptr: no tally, no kernel
   ganon_dtally *st_tally = nullptr;

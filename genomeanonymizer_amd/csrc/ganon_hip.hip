@@ -513,6 +513,7 @@ GANON_API int ganon_ctx_destroy(ganon_ctx *ctx) {
   if (ctx->join_ev) hipEventDestroy(ctx->join_ev);
   for (auto &b : ctx->dcache) hipFree(b.second);
   if (ctx->ks_block) hipFree(ctx->ks_block);
+  if (ctx->sa_block) hipFree(ctx->sa_block);
   ganon_inflate_free(ctx->inflate);
   ganon_deflate_free(ctx->deflate);
   delete ctx;

@@ -22,6 +22,7 @@
 #include "../../include/ganon_host.h"
 #include "ganon_name_hash.h"
 #include "ganon_known_sites.h"
+#include "ganon_sa_clips.h"
 #include "ganon_site_tally.h"
 
 namespace {
@@ -181,6 +182,7 @@ struct ganon_bam {
   ganon_buf_free_fn ext_free = nullptr;
   ganon_bam_view ext{};
   int64_t known_masked = 0;   // --known_sites: bases records_to_columns rewrote in this table
+  int64_t sa_masked = 0, sa_ignored = 0;   // --mask_sa_clips: clip bases it rewrote through SA, entries it ignored
   ganon_bam() = default;
   ganon_bam(const ganon_bam &) = delete;
   ganon_bam &operator=(const ganon_bam &) = delete;
@@ -203,10 +205,20 @@ struct SitesData {
   std::vector<int32_t> pos;
   std::vector<uint8_t> code;
   ganon_ks::View view;
+  // --mask_sa_clips (ganon_sites_set_sa_clips): the header's names, sorted, and the switch
+  std::vector<char> sa_blob;
+  std::vector<int64_t> sa_off;
+  std::vector<int32_t> sa_tid;
+  ganon_sa::Names sa_names;
+  bool sa_on = false;
+  // (a table without sites rewrites nothing: its tags are not walked or counted, as on the device,
+  // where such a table is no table)
+  const ganon_sa::Names *sa() const { return sa_on && !pos.empty() ? &sa_names : nullptr; }
 };
 struct ganon_sites {
   std::shared_ptr<const SitesData> data;
 };
+static const ganon_sa::Names *sa_of(const ganon_sites *s) { return s ? s->data->sa() : nullptr; }
 
 // --discover_sites: the evidence tally (ganon_site_tally.h) of one run's sequences, a byte array per
 // sequence made zeroed when the first evidence on it arrives; shared by the handle and every reader it
@@ -358,10 +370,13 @@ int parse_header(const uint8_t *d, int64_t n, ganon_bam *bam, int64_t &p) {
 // With sites (--known_sites) the panel mask (ganon_known_sites.h) rewrites each record's bases, and
 // with a quality their quality bytes, in the table right after they are copied, on the same threads;
 // bam->known_masked counts the rewritten bases. With tally (--discover_sites) each record's evidence is
-// OR-ed into the tally (ganon_site_tally.h) at the same place, before any mask.
+// OR-ed into the tally (ganon_site_tally.h) at the same place, before any mask. With sa as well
+// (--mask_sa_clips) the record's soft-clipped bases are masked along its SA alignments
+// (ganon_sa_clips.h) right after the panel mask; bam->sa_masked and bam->sa_ignored count.
 int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, int threads,
                        const std::vector<int64_t> *known = nullptr, const ganon_nh::KeyState *ks = nullptr,
-                       const ganon_ks::View *sites = nullptr, const TallyUse *tally = nullptr) {
+                       const ganon_ks::View *sites = nullptr, const TallyUse *tally = nullptr,
+                       const ganon_sa::Names *sa = nullptr) {
   const int nt = std::max(1, std::min(threads, 64));
   // ---- records: boundaries (sequential), sizes + offsets, then columns in parallel ----
   std::vector<int64_t> own;   // offset of each record's block_size field
@@ -431,9 +446,9 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
   huge_resize(bam->qual, (size_t)o_qual[nr]);
   huge_resize(bam->aux, (size_t)o_aux[nr]);
   lap(kPhSizes, tph);
-  std::atomic<int64_t> masked{0};
+  std::atomic<int64_t> masked{0}, sa_masked{0}, sa_ignored{0};
   run_chunks([&](int64_t i0, int64_t i1) {
-    int64_t mine = 0;
+    int64_t mine = 0, sa_mine = 0, sa_ign = 0;
     for (int64_t i = i0; i < i1; ++i) {
       const uint8_t *r = d + rec[i] + 4;
       int32_t bs, rtid, rpos, mtid, mpos, rtlen, lseq;
@@ -503,10 +518,20 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
       if (sites)
         mine += ganon_ks::mask_record(*sites, rtid, rpos, rflag, ncig, lseq, cg, bam->seq.data() + o_seq[i],
                                       bam->qual.data() + o_qual[i]);
+      if (sites && sa) {
+        int ign = 0;
+        sa_mine += ganon_sa::mask_record(*sites, *sa, rtid, rflag, ncig, lseq, cg, bam->seq.data() + o_seq[i],
+                                         bam->qual.data() + o_qual[i], bam->aux.data() + o_aux[i], bs - q, &ign);
+        sa_ign += ign;
+      }
     }
     if (mine) masked.fetch_add(mine, std::memory_order_relaxed);
+    if (sa_mine) sa_masked.fetch_add(sa_mine, std::memory_order_relaxed);
+    if (sa_ign) sa_ignored.fetch_add(sa_ign, std::memory_order_relaxed);
   });
   bam->known_masked += masked.load();
+  bam->sa_masked += sa_masked.load();
+  bam->sa_ignored += sa_ignored.load();
   lap(kPhColumns, tph);
   if (tally && tally->data->failed.load()) return set_err("out of memory allocating a site tally");
   return 0;
@@ -516,7 +541,8 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
 }  // namespace
 
 static int bam_open_impl(const char *path, int threads, ganon_bam **out, const ganon_nh::KeyState *ks = nullptr,
-                         const ganon_ks::View *sites = nullptr, const TallyUse *tally = nullptr) {
+                         const ganon_ks::View *sites = nullptr, const TallyUse *tally = nullptr,
+                         const ganon_sa::Names *sa = nullptr) {
   FILE *fh = std::fopen(path, "rb");
   if (!fh) return set_err(std::string("cannot open ") + path);
   std::fseek(fh, 0, SEEK_END);
@@ -553,7 +579,7 @@ static int bam_open_impl(const char *path, int threads, ganon_bam **out, const g
     delete bam;
     return hr < 0 ? -1 : set_err("truncated header");
   }
-  if (records_to_columns(data.data(), p, (int64_t)data.size(), bam, threads, nullptr, ks, sites, tally) != 0) {
+  if (records_to_columns(data.data(), p, (int64_t)data.size(), bam, threads, nullptr, ks, sites, tally, sa) != 0) {
     delete bam;
     return -1;
   }
@@ -636,7 +662,7 @@ GANON_HOST_API int ganon_bam_open_ex(const char *path, int threads, const uint8_
   ganon_nh::KeyState ks;
   if (key_len > 0) ganon_nh::key_state(key, key_len, &ks);
   try {
-    return bam_open_impl(path, threads, out, key_len > 0 ? &ks : nullptr, sites ? &sites->data->view : nullptr);
+    return bam_open_impl(path, threads, out, key_len > 0 ? &ks : nullptr, sites ? &sites->data->view : nullptr, nullptr, sa_of(sites));
   } catch (const std::bad_alloc &) {
     return set_err("out of memory decoding the BAM file");
   } catch (const std::exception &e) {
@@ -645,6 +671,45 @@ GANON_HOST_API int ganon_bam_open_ex(const char *path, int threads, const uint8_
 }
 
 GANON_HOST_API int64_t ganon_bam_known_sites_masked(const ganon_bam *b) { return b ? b->known_masked : 0; }
+
+GANON_HOST_API int ganon_sites_set_sa_clips(ganon_sites *s, int32_t n_names, const char *names, const int64_t *name_off,
+                                            const int32_t *name_tid, int on) {
+  if (!s || n_names < 0 || (n_names > 0 && (!names || !name_off || !name_tid)))
+    return set_err("ganon_sites_set_sa_clips: bad arguments");
+  if (n_names > 0 && name_off[0] != 0) return set_err("ganon_sites_set_sa_clips: name_off[0] must be 0");
+  for (int32_t i = 0; i < n_names; ++i) {
+    if (name_off[i + 1] < name_off[i]) return set_err("ganon_sites_set_sa_clips: name_off must not decrease");
+    if (name_tid[i] < 0 || name_tid[i] >= s->data->view.n_ref)
+      return set_err("ganon_sites_set_sa_clips: a name's sequence id is outside the table");
+    if (i > 0) {   // strictly increasing, bytewise
+      const int64_t la = name_off[i] - name_off[i - 1], lb = name_off[i + 1] - name_off[i];
+      const int c = std::memcmp(names + name_off[i - 1], names + name_off[i], (size_t)std::min(la, lb));
+      if (c > 0 || (c == 0 && la >= lb)) return set_err("ganon_sites_set_sa_clips: the names must be sorted and distinct");
+    }
+  }
+  try {   // (a copy: readers and tables made with the handle before keep what they had)
+    auto d = std::make_shared<SitesData>(*s->data);
+    d->view.off = d->off.data();
+    d->view.pos = d->pos.data();
+    d->view.code = d->code.data();
+    d->sa_off.assign(1, 0);
+    if (n_names > 0) d->sa_off.assign(name_off, name_off + n_names + 1);
+    d->sa_blob.assign(names, names + (n_names > 0 ? name_off[n_names] : 0));
+    d->sa_tid.assign(name_tid, name_tid + n_names);
+    d->sa_names.n = n_names;
+    d->sa_names.off = d->sa_off.data();
+    d->sa_names.blob = d->sa_blob.data();
+    d->sa_names.tid = d->sa_tid.data();
+    d->sa_on = on != 0;
+    s->data = std::move(d);
+    return 0;
+  } catch (const std::bad_alloc &) {
+    return set_err("out of memory copying the sequence names");
+  }
+}
+
+GANON_HOST_API int64_t ganon_bam_sa_clips_masked(const ganon_bam *b) { return b ? b->sa_masked : 0; }
+GANON_HOST_API int64_t ganon_bam_sa_entries_ignored(const ganon_bam *b) { return b ? b->sa_ignored : 0; }
 
 GANON_HOST_API int ganon_site_tally_create(int32_t n_seq, const uint8_t *nt16, const int64_t *nib_off, const int64_t *len,
                                            ganon_site_tally **out) {
@@ -739,7 +804,7 @@ GANON_HOST_API int ganon_bam_open_ex2(const char *path, int threads, const uint8
   try {
     std::unique_ptr<TallyUse> use;
     if (tally && !(use = tally_use(tally, dataset, seq_of_tid, n_tid))) return -1;
-    return bam_open_impl(path, threads, out, key_len > 0 ? &ks : nullptr, sites ? &sites->data->view : nullptr, use.get());
+    return bam_open_impl(path, threads, out, key_len > 0 ? &ks : nullptr, sites ? &sites->data->view : nullptr, use.get(), sa_of(sites));
   } catch (const std::bad_alloc &) {
     return set_err("out of memory decoding the BAM file");
   } catch (const std::exception &e) {
@@ -863,6 +928,7 @@ struct ganon_bam_reader {
   ganon_nh::KeyState name_key{};
   std::shared_ptr<const SitesData> sites;   // ganon_bam_reader_set_known_sites: the panel mask of its tables
   int64_t known_masked = 0;                 // ... and the bases its host decodes rewrote so far
+  int64_t sa_masked = 0, sa_ignored = 0;    // --mask_sa_clips: the same for clip bases through SA; entries ignored
   std::unique_ptr<TallyUse> tally;          // ganon_bam_reader_set_site_tally: the evidence tally of its tables
 };
 
@@ -1356,6 +1422,8 @@ GANON_HOST_API int ganon_bam_reader_set_known_sites(ganon_bam_reader *R, const g
 }
 
 GANON_HOST_API int64_t ganon_bam_reader_known_sites_masked(const ganon_bam_reader *R) { return R ? R->known_masked : 0; }
+GANON_HOST_API int64_t ganon_bam_reader_sa_clips_masked(const ganon_bam_reader *R) { return R ? R->sa_masked : 0; }
+GANON_HOST_API int64_t ganon_bam_reader_sa_entries_ignored(const ganon_bam_reader *R) { return R ? R->sa_ignored : 0; }
 
 GANON_HOST_API int ganon_bam_reader_set_site_tally(ganon_bam_reader *R, const ganon_site_tally *tally, int32_t dataset,
                                                    const int32_t *seq_of_tid, int32_t n_tid) {
@@ -1420,11 +1488,13 @@ GANON_HOST_API int ganon_bam_reader_contig(ganon_bam_reader *R, int32_t tid, gan
     bam->ref_name_off = R->header.ref_name_off;
     bam->ref_len = R->header.ref_len;
     if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs, R->hashed ? &R->name_key : nullptr,
-                           R->sites ? &R->sites->view : nullptr, R->tally.get()) != 0) {
+                           R->sites ? &R->sites->view : nullptr, R->tally.get(), R->sites ? R->sites->sa() : nullptr) != 0) {
       delete bam;
       return -1;
     }
     R->known_masked += bam->known_masked;
+    R->sa_masked += bam->sa_masked;
+    R->sa_ignored += bam->sa_ignored;
     *out = bam;
     return 0;
   } catch (const std::bad_alloc &) {
@@ -1482,11 +1552,13 @@ GANON_HOST_API int ganon_bam_reader_region(ganon_bam_reader *R, int32_t tid, int
       return 0;
     }
     if (records_to_columns(data.data(), 0, (int64_t)data.size(), bam, R->threads, &recs, R->hashed ? &R->name_key : nullptr,
-                           R->sites ? &R->sites->view : nullptr, R->tally.get()) != 0) {
+                           R->sites ? &R->sites->view : nullptr, R->tally.get(), R->sites ? R->sites->sa() : nullptr) != 0) {
       delete bam;
       return -1;
     }
     R->known_masked += bam->known_masked;
+    R->sa_masked += bam->sa_masked;
+    R->sa_ignored += bam->sa_ignored;
     *out = bam;
     return 0;
   } catch (const std::bad_alloc &) {

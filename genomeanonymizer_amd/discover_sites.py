@@ -34,7 +34,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import native
-from .known_sites import PairPanel, Panel, panel_default
+from .known_sites import PairPanel, Panel, mask_sa_clips_default, panel_default
 
 log = logging.getLogger("genomeanonymizer_amd")
 
@@ -255,7 +255,8 @@ def pair_default(fasta, windows, tumor_bam: str, normal_bam: str, threads: int =
                  window_bytes: int = 0, timing: Optional[dict] = None) -> Optional[PairPanel]:
     """What the pipelines decode one pair with (None: both options off): the panel of ``--known_sites``
     OR-ed with the sites ``--discover_sites`` finds in the pair's own BAMs, less the pair's own SNVs,
-    rewritten bases at ``GANON_MASKED_BASE_QUALITY`` when that option is on too."""
+    rewritten bases at ``GANON_MASKED_BASE_QUALITY`` when that option is on too, soft clips masked along
+    their SA alignments with ``GANON_MASK_SA_CLIPS=1``."""
     panel = panel_default(fasta)
     if default_on():
         stats: dict = {}
@@ -267,4 +268,4 @@ def pair_default(fasta, windows, tumor_bam: str, normal_bam: str, threads: int =
         panel = merge(panel, found)
     if panel is None:
         return None
-    return PairPanel(panel, windows, native.masked_base_quality_default())
+    return PairPanel(panel, windows, native.masked_base_quality_default(), mask_sa_clips_default())

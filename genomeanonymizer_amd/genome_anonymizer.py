@@ -3,7 +3,7 @@
   python -m genomeanonymizer_amd.genome_anonymizer -d DIR -s samples.tsv -r ref.fa \\
       [-m complete_germline] [-c CPUS] [--record_statistics] [--enhanced_multiprocessing] [-v N]
       [--compress_output] [--masked_base_quality Q] [--hash_read_names] [--known_sites PANEL.vcf[.gz]]
-      [--discover_sites]
+      [--discover_sites] [--mask_sa_clips]
 
 samples.tsv: tumor<TAB>normal<TAB>vcf per line, paths relative to DIR, '#' lines skipped.
 Outputs next to the inputs: re.sub('.bam|.sam|.cram', '.anonymized', path) + .1/.2.fastq
@@ -33,8 +33,8 @@ base: a mismatch, two REFs at one position, a position past the contig's end or 
 the run before any output file is opened. The positions of each pair's own VCF SNVs are left out of
 the panel for that pair: those calls are what the product keeps. With --masked_base_quality Q the
 rewritten bases are printed with quality Q too. Limits: a supplementary record is masked along its own
-alignment, the primary's soft-clipped copy of those bases is not; indels and MNVs of the panel are not
-used. Each process logs how many bases it rewrote.
+alignment, the primary's soft-clipped copy of those bases is not (--mask_sa_clips closes this); indels
+and MNVs of the panel are not used. Each process logs how many bases it rewrote.
 --discover_sites (an extension; --no-discover_sites; GANON_DISCOVER_SITES=1 is the same default): the
 panel the pair's own BAMs give. Before a pair's jobs start a pre-pass decodes both BAMs once more and
 notes, per reference position, which alleles other than the reference's the tumor reads and the normal
@@ -46,8 +46,22 @@ a site that shows its ALT becomes the reference base where its record is decoded
 --masked_base_quality Q its quality becomes Q. With --known_sites as well the two tables are OR-ed. The
 run writes exactly what a run without the option writes on BAMs rewritten that way. The discovered list
 is the donor's germline SNV list: it is never logged or written, the log gives counts only. Limits:
-indels are not discovered; a supplementary record's bases in the primary's soft clip are not masked;
-the pre-pass decodes every record a second time.
+indels are not discovered; a supplementary record's bases in the primary's soft clip are not masked
+(--mask_sa_clips closes this); the pre-pass decodes every record a second time.
+--mask_sa_clips (an extension; --no-mask_sa_clips; GANON_MASK_SA_CLIPS=1 is the same default): with a
+table (--known_sites, --discover_sites or both; without one the option is a command-line error) the mask
+also follows each record's SA:Z tag. A chimeric read's primary record holds the whole sequence, and the
+bases it soft-clips are aligned only in the supplementary record; the written sequence comes from the
+primary. For every record with a soft clip, each SA entry rname,pos,strand,CIGAR,mapQ,NM is projected
+onto the read as the SAM specification says (reverse-complemented when the entry's strand is not the
+record's), and a clipped base that the entry aligns (M, =, X) to a listed position and that shows a
+listed ALT becomes the reference base, with --masked_base_quality Q its quality Q. Aligned, inserted and
+hard-clipped bases are never touched through SA. An entry is used whole or not at all: six fields, a
+header sequence name, pos 1..2^31-1, strand + or -, a well-formed CIGAR whose query length is the full
+read's; other entries are ignored and counted. The run writes what a run without the option writes on
+BAMs rewritten that way. Limits: secondary alignments carry no clips and are untouched; --discover_sites
+still takes its evidence from aligned bases only; a supplementary record whose bases the aligner did not
+reverse-complement for its strand is projected as the specification says, not as that file holds them.
 
 Multi-GPU: launch under ``torchrun --nproc-per-node N`` (or set WORLD_SIZE/RANK/LOCAL_RANK):
 contigs are sharded round-robin over the ranks; each rank decodes, masks and writes its own
@@ -104,6 +118,9 @@ def exec_parser(argv=None):
                         help="Mask every SNV allele that a tumor read and a normal read of the pair both show, "
                              "genome-wide: a pre-pass over both BAMs builds the pair's own site table (default: "
                              "GANON_DISCOVER_SITES)")
+    parser.add_argument("--mask_sa_clips", action=BooleanOptionalAction,
+                        help="With --known_sites and / or --discover_sites: mask soft-clipped bases too, along the "
+                             "alignments the record's SA tag names (default: GANON_MASK_SA_CLIPS)")
     parser.add_argument("-v", "--verbose", type=int, required=False, default=2, help="Verbosity of logging")
     parser.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     return parser.parse_args(argv)
@@ -147,6 +164,12 @@ def run_anonymizer(argv=None) -> None:
         os.environ["GANON_KNOWN_SITES"] = config.known_sites
     if config.discover_sites is not None:
         os.environ["GANON_DISCOVER_SITES"] = "1" if config.discover_sites else "0"
+    if config.mask_sa_clips is not None:
+        os.environ["GANON_MASK_SA_CLIPS"] = "1" if config.mask_sa_clips else "0"
+    if (os.environ.get("GANON_MASK_SA_CLIPS", "0") == "1" and not os.environ.get("GANON_KNOWN_SITES")
+            and os.environ.get("GANON_DISCOVER_SITES", "0") != "1"):   # (before any file is opened)
+        logging.error("--mask_sa_clips needs a site table: give --known_sites PANEL.vcf[.gz], --discover_sites or both")
+        sys.exit(1)
     from . import native
     try:   # (a malformed key ends the run here, before any file is opened)
         if os.environ.get("GANON_HASH_READ_NAMES", "0") == "1" and native.NAME_KEY_ENV in os.environ:

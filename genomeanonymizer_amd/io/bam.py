@@ -113,6 +113,9 @@ class ReadTable:
         lib.ganon_bam_view_get(h, C.byref(v))
         self._load(path, v, owner)
         self.known_masked = int(lib.ganon_bam_known_sites_masked(h))
+        # --mask_sa_clips (a table with sa_clips): clip bases rewritten through SA tags, entries ignored
+        self.sa_masked = int(lib.ganon_bam_sa_clips_masked(h))
+        self.sa_ignored = int(lib.ganon_bam_sa_entries_ignored(h))
         self._finish()
 
     def _load(self, path: str, v, owner: _Decoded) -> None:
@@ -313,6 +316,7 @@ class BamReader:
         self.known_sites = None
         self.site_tally = None
         self._dev_masked0 = 0
+        self._dev_sa0 = (0, 0)
         v = native.BamView()
         lib.ganon_bam_reader_header(h, C.byref(v))
         off = _arr(v.ref_name_off, v.n_ref, np.int64)
@@ -341,6 +345,10 @@ class BamReader:
         if hasattr(inflater, "set_known_sites"):
             inflater.set_known_sites(self.known_sites)   # (set or cleared on every attach, as the key)
             self._dev_masked0 = inflater.known_sites_masked() if self.known_sites is not None else 0
+            if getattr(self.known_sites, "sa_clips", False):
+                if not hasattr(inflater, "sa_clips_counts"):
+                    raise native.GanonError("this inflater cannot mask SA clips (no sa_clips_counts)")
+                self._dev_sa0 = inflater.sa_clips_counts()
         elif self.known_sites is not None:
             raise native.GanonError("this inflater cannot mask known sites (no set_known_sites)")
         native.host_lib().ganon_bam_reader_set_inflater(self._h, inflater.fn, inflater.handle, inflater.min_blocks)
@@ -373,6 +381,19 @@ class BamReader:
                                                len(seq_of)) != 0:
             raise native.GanonError(lib.ganon_host_last_error().decode())
         self.site_tally = (tally, int(dataset))   # (kept alive: the reader's threads read its genome)
+
+    def sa_clips_counts(self) -> dict:
+        """--mask_sa_clips: clip bases rewritten through SA tags by this reader's host decodes and, since
+        it was attached, by its inflater's context, and the SA entries both ignored."""
+        lib = native.host_lib()
+        out = {"host": int(lib.ganon_bam_reader_sa_clips_masked(self._h)) if self._h else 0, "device": 0,
+               "ignored": int(lib.ganon_bam_reader_sa_entries_ignored(self._h)) if self._h else 0}
+        if (getattr(self.known_sites, "sa_clips", False) and self.inflater is not None
+                and hasattr(self.inflater, "sa_clips_counts")):
+            m, g = self.inflater.sa_clips_counts()
+            out["device"] = m - self._dev_sa0[0]
+            out["ignored"] += g - self._dev_sa0[1]
+        return out
 
     def known_masked(self) -> int:
         """--known_sites: bases rewritten in this reader's tables so far, by its host decodes
@@ -429,6 +450,7 @@ class BamReader:
         t.qual = np.zeros(0, np.uint8)
         t.aux = np.zeros(0, np.uint8)
         t.known_masked = 0
+        t.sa_masked = t.sa_ignored = 0
         t._finish()
         return t
 

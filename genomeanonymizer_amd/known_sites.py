@@ -40,6 +40,7 @@ from .variants import VariantType
 log = logging.getLogger("genomeanonymizer_amd")
 
 ENV = "GANON_KNOWN_SITES"
+SA_ENV = "GANON_MASK_SA_CLIPS"    # --mask_sa_clips: soft clips masked along their SA alignments
 NT16_OF = {"A": 1, "C": 2, "G": 4, "T": 8}
 
 
@@ -126,17 +127,44 @@ def load_panel(path: str, fasta) -> Panel:
     return Panel(path, contigs, stats)
 
 
+def mask_sa_clips_default() -> bool:
+    """``GANON_MASK_SA_CLIPS=1`` (``--mask_sa_clips``), for library callers and for spawned pair workers
+    and ranks."""
+    return os.environ.get(SA_ENV, "0") == "1"
+
+
+def sorted_names(ref_names: Sequence[str]) -> Tuple[bytes, np.ndarray, np.ndarray]:
+    """The header's names for the SA rule's binary search: sorted bytewise and distinct (a name listed
+    twice: its first sequence), as (blob, name_off int64 [n + 1], name_tid int32 [n])."""
+    first: Dict[bytes, int] = {}
+    for t, name in enumerate(ref_names):
+        first.setdefault(name.encode(), t)
+    names = sorted(first)
+    off = np.zeros(len(names) + 1, np.int64)
+    if names:
+        off[1:] = np.cumsum([len(b) for b in names])
+    return b"".join(names), off, np.asarray([first[b] for b in names], np.int32)
+
+
 class SitesTable:
     """The table one decoder takes: per BAM sequence id the slice [site_off[t], site_off[t + 1]) of
     ``site_pos`` / ``site_code``, and the quality a rewritten base gets (-1: qualities stay). ``handle``
-    is the host library's ``ganon_sites`` (made on first use, destroyed with this object)."""
+    is the host library's ``ganon_sites`` (made on first use, destroyed with this object). With
+    ``sa_clips`` (--mask_sa_clips) and the header's ``ref_names`` the decoders also mask each record's
+    soft clips along its SA alignments (csrc/ganon_sa_clips.h)."""
 
-    def __init__(self, site_off: np.ndarray, site_pos: np.ndarray, site_code: np.ndarray, quality: int = -1):
+    def __init__(self, site_off: np.ndarray, site_pos: np.ndarray, site_code: np.ndarray, quality: int = -1,
+                 ref_names: Optional[Sequence[str]] = None, sa_clips: bool = False):
         self.site_off = np.ascontiguousarray(site_off, np.int64)
         self.site_pos = np.ascontiguousarray(site_pos, np.int32)
         self.site_code = np.ascontiguousarray(site_code, np.uint8)
         self.quality = int(quality)
         self.n_ref = len(self.site_off) - 1
+        self.sa_clips = bool(sa_clips)
+        if self.sa_clips:
+            if ref_names is None or len(ref_names) != self.n_ref:
+                raise native.GanonError("mask_sa_clips: the table needs the BAM header's sequence names")
+            self.sa_blob, self.sa_off, self.sa_tid = sorted_names(ref_names)
         self._h = None
 
     @property
@@ -153,6 +181,12 @@ class SitesTable:
                                         self.site_code.ctypes.data_as(native._u8p), self.quality, C.byref(h))
             if rc != 0:
                 raise native.GanonError(lib.ganon_host_last_error().decode())
+            if self.sa_clips and lib.ganon_sites_set_sa_clips(h, len(self.sa_tid), self.sa_blob,
+                                                              native._ptr(self.sa_off, native._i64p),
+                                                              native._ptr(self.sa_tid, native._i32p), 1) != 0:
+                msg = lib.ganon_host_last_error().decode()
+                lib.ganon_sites_destroy(h)
+                raise native.GanonError(msg)
             self._h = h
         return self._h
 
@@ -179,9 +213,10 @@ def own_snv_positions(windows: Iterable) -> Dict[str, np.ndarray]:
 class PairPanel:
     """A panel less one pair's own SNV positions; ``table(ref_names)`` is cached by BAM header."""
 
-    def __init__(self, panel: Panel, windows: Iterable = (), quality: Optional[int] = None):
+    def __init__(self, panel: Panel, windows: Iterable = (), quality: Optional[int] = None, sa_clips: bool = False):
         self.panel = panel
         self.quality = -1 if quality is None else int(quality)
+        self.sa_clips = bool(sa_clips)   # --mask_sa_clips: every table carries its header's names and the switch
         own = own_snv_positions(windows)
         self.contigs: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
         self.excluded = 0
@@ -212,7 +247,8 @@ class PairPanel:
             log.info("known sites: %d sites on the BAM's %d sequences (%d of the pair's own SNV positions left out), "
                      "%d panel contigs not in the BAM header ignored", int(off[-1]), len(key), self.excluded, len(ignored))
             t = self._tables[key] = SitesTable(off, np.concatenate(ps) if ps else np.zeros(0, np.int32),
-                                               np.concatenate(cs) if cs else np.zeros(0, np.uint8), self.quality)
+                                               np.concatenate(cs) if cs else np.zeros(0, np.uint8), self.quality,
+                                               key, self.sa_clips)
         return t
 
 
@@ -235,11 +271,12 @@ def panel_default(fasta) -> Optional[Panel]:
 
 def pair_default(fasta, windows: Iterable) -> Optional[PairPanel]:
     """What the pipelines decode one pair with (None: the option is off): the default panel less the
-    pair's own SNVs, rewritten bases at ``GANON_MASKED_BASE_QUALITY`` when that option is on too."""
+    pair's own SNVs, rewritten bases at ``GANON_MASKED_BASE_QUALITY`` when that option is on too, soft
+    clips masked along their SA alignments with ``GANON_MASK_SA_CLIPS=1``."""
     panel = panel_default(fasta)
     if panel is None:
         return None
-    return PairPanel(panel, windows, native.masked_base_quality_default())
+    return PairPanel(panel, windows, native.masked_base_quality_default(), mask_sa_clips_default())
 
 
 def resolve(known_sites, ref_names: Sequence[str]) -> Optional[SitesTable]:

@@ -224,6 +224,8 @@ def hip_lib():
     lib.ganon_ctx_set_name_key.argtypes = [_p, C.c_char_p, C.c_int32]
     lib.ganon_ctx_set_known_sites.argtypes = [_p, C.c_int32, _i64p, _i32p, _u8p, C.c_int64, C.c_int32]
     lib.ganon_ctx_known_sites_masked.argtypes = [_p, _i64p]
+    lib.ganon_ctx_set_sa_clips.argtypes = [_p, C.c_int32, C.c_char_p, _i64p, _i32p]
+    lib.ganon_ctx_sa_clips_counts.argtypes = [_p, _i64p, _i64p]
     lib.ganon_dtally_create.argtypes = [_p, _u8p, C.c_int64, C.POINTER(_p)]
     lib.ganon_site_compact_tile.argtypes = []
     lib.ganon_ctx_set_site_tally.argtypes = [_p, _p, C.c_int32, C.c_int32]
@@ -270,6 +272,7 @@ EXPORTED_HIP_SYMBOLS = (
     "ganon_inflate", "ganon_inflate_hostcb", "ganon_inflate_device_output",
     "ganon_bam_columns", "ganon_bam_dcols_get", "ganon_bam_dcols_download", "ganon_bam_dcols_free",
     "ganon_bam_walk_params", "ganon_ctx_set_name_key", "ganon_ctx_set_known_sites", "ganon_ctx_known_sites_masked",
+    "ganon_ctx_set_sa_clips", "ganon_ctx_sa_clips_counts",
     "ganon_site_compact_tile", "ganon_dtally_create", "ganon_ctx_set_site_tally", "ganon_dtally_compact",
     "ganon_dtally_sites", "ganon_dtally_free",
     "ganon_pinned_alloc", "ganon_pinned_free", "ganon_pinned_stats", "ganon_region_decode",
@@ -290,6 +293,8 @@ EXPORTED_HOST_SYMBOLS = (
     "ganon_bam_open_keyed", "ganon_names_hash", "ganon_bam_reader_set_name_key",
     "ganon_sites_create", "ganon_sites_destroy", "ganon_bam_open_ex", "ganon_bam_known_sites_masked",
     "ganon_bam_reader_set_known_sites", "ganon_bam_reader_known_sites_masked",
+    "ganon_sites_set_sa_clips", "ganon_bam_sa_clips_masked", "ganon_bam_sa_entries_ignored",
+    "ganon_bam_reader_sa_clips_masked", "ganon_bam_reader_sa_entries_ignored",
     "ganon_site_tally_create", "ganon_site_tally_destroy", "ganon_site_tally_bytes", "ganon_site_tally_count",
     "ganon_site_tally_finish", "ganon_site_tally_release", "ganon_bam_open_ex2", "ganon_bam_reader_set_site_tally",
 )
@@ -460,11 +465,20 @@ class GpuInflater:
         """--known_sites: the context's BAM decoder (``bam_columns``, the region decoder) applies the
         panel mask of ``table`` (a known_sites.SitesTable) from now on: the table is uploaded to device
         memory (``ganon_ctx_set_known_sites``) and stays there until it is replaced; None or a table
-        without sites clears it. Setting the table already in place does nothing."""
+        without sites clears it. Setting the table already in place does nothing. A table with
+        ``sa_clips`` (--mask_sa_clips) brings its header's names (``ganon_ctx_set_sa_clips``:
+        k_bam_sa_clips after k_bam_known_mask); any other table clears them."""
         if table is not None and table.n == 0:
             table = None
         if table is self.known_sites:
             return
+        if table is not None and getattr(table, "sa_clips", False):
+            rc = self._lib.ganon_ctx_set_sa_clips(self._h, len(table.sa_tid), table.sa_blob, _ptr(table.sa_off, _i64p),
+                                                  _ptr(table.sa_tid, _i32p))
+        else:
+            rc = self._lib.ganon_ctx_set_sa_clips(self._h, 0, None, None, None)
+        if rc != 0:
+            raise GanonError(self._lib.ganon_last_error(self._h).decode(errors="replace"))
         if table is None:
             rc = self._lib.ganon_ctx_set_known_sites(self._h, 0, None, None, None, 0, -1)
         else:
@@ -482,6 +496,14 @@ class GpuInflater:
         if self._lib.ganon_ctx_known_sites_masked(self._h, C.byref(c)) != 0:
             raise GanonError(self._lib.ganon_last_error(self._h).decode(errors="replace"))
         return int(c.value)
+
+    def sa_clips_counts(self) -> Tuple[int, int]:
+        """--mask_sa_clips: the clip bases the context's decoder rewrote through SA tags and the SA entries
+        it ignored so far (``ganon_ctx_sa_clips_counts``)."""
+        m, g = C.c_int64(0), C.c_int64(0)
+        if self._lib.ganon_ctx_sa_clips_counts(self._h, C.byref(m), C.byref(g)) != 0:
+            raise GanonError(self._lib.ganon_last_error(self._h).decode(errors="replace"))
+        return int(m.value), int(g.value)
 
     def set_site_tally(self, tally, dataset: int = 0, tid: int = -1) -> None:
         """--discover_sites: the context's BAM decoder (``bam_columns``, the region decoder) ORs the
@@ -1900,6 +1922,11 @@ def host_lib():
     lib.ganon_bam_reader_set_known_sites.argtypes = [_p, _p]
     lib.ganon_bam_reader_known_sites_masked.argtypes = [_p]
     lib.ganon_bam_reader_known_sites_masked.restype = C.c_int64
+    lib.ganon_sites_set_sa_clips.argtypes = [_p, C.c_int32, C.c_char_p, _i64p, _i32p, C.c_int]
+    for f in (lib.ganon_bam_sa_clips_masked, lib.ganon_bam_sa_entries_ignored, lib.ganon_bam_reader_sa_clips_masked,
+              lib.ganon_bam_reader_sa_entries_ignored):
+        f.argtypes = [_p]
+        f.restype = C.c_int64
     lib.ganon_site_tally_create.argtypes = [C.c_int32, _u8p, _i64p, _i64p, C.POINTER(_p)]
     lib.ganon_site_tally_destroy.argtypes = [_p]
     lib.ganon_site_tally_destroy.restype = None

@@ -76,6 +76,10 @@ def anonymize_genome(windows_in_sample: List[Window], tumor_bam_file: str, norma
     if known is not None:
         log.info("known sites: %d bases rewritten by this process's decodes (tumor and normal)",
                  tumor.known_masked + normal.known_masked)
+        if known.sa_clips:
+            log.info("SA clips: %d clip bases rewritten (host %d, device 0), %d SA entries ignored",
+                     tumor.sa_masked + normal.sa_masked, tumor.sa_masked + normal.sa_masked,
+                     tumor.sa_ignored + normal.sa_ignored)
     if has_split_alignments(tumor) or has_split_alignments(normal):
         log.info("secondary / supplementary alignments or SA tags: the sample streams contig by contig")
         del tumor, normal   # (the streamed path decodes job by job: do not hold the whole sample too)

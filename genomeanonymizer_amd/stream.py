@@ -1624,6 +1624,13 @@ def anonymize_genome_streaming(windows: List[Window], tumor_bam: str, normal_bam
             logging.getLogger("genomeanonymizer_amd").info(
                 "known sites: %d bases rewritten by this process's decodes (tumor and normal)",
                 timing["known_sites_masked"])
+            if known.sa_clips:
+                sa = [r.sa_clips_counts() for r in list(readers) + list(redo_readers)]
+                timing["sa_clips_masked"] = sum(c["host"] + c["device"] for c in sa)
+                timing["sa_entries_ignored"] = sum(c["ignored"] for c in sa)
+                logging.getLogger("genomeanonymizer_amd").info(
+                    "SA clips: %d clip bases rewritten (host %d, device %d), %d SA entries ignored", timing["sa_clips_masked"],
+                    sum(c["host"] for c in sa), sum(c["device"] for c in sa), timing["sa_entries_ignored"])
         # the readers' file mappings go on a thread of their own (unmapping a chromosome's BAM
         # took part of every rank's tail; nothing waits for it)
         threading.Thread(target=_close_all, args=(list(readers) + list(redo_readers),), daemon=True).start()

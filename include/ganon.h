@@ -481,6 +481,18 @@ GANON_API int ganon_ctx_set_name_key(ganon_ctx *ctx, const uint8_t *key, int32_t
 GANON_API int ganon_ctx_set_known_sites(ganon_ctx *ctx, int32_t n_ref, const int64_t *site_off, const int32_t *site_pos,
                                         const uint8_t *site_code, int64_t n, int32_t quality);
 GANON_API int ganon_ctx_known_sites_masked(ganon_ctx *ctx, int64_t *masked);
+/* --mask_sa_clips (additive; the ABI version stays 5). ganon_ctx_set_sa_clips uploads the BAM header's
+ * sequence names (the layout and the rule of include/ganon_host.h ganon_sites_set_sa_clips: sorted
+ * bytewise and distinct, name_off[n_names + 1], name_tid; checked here as there), where they stay until
+ * they are replaced or cleared (n_names = 0). With names AND a known-sites table, ganon_bam_columns and
+ * ganon_region_decode on this context run k_bam_sa_clips right after k_bam_known_mask, over the columns
+ * in device memory, and return the bytes the host decoder returns with the same table and names. Without
+ * names no kernel is added. ganon_ctx_sa_clips_counts: the clip bases rewritten through SA tags and the
+ * SA entries ignored on this context so far (it waits for the context's stream); neither is part of
+ * ganon_ctx_known_sites_masked. */
+GANON_API int ganon_ctx_set_sa_clips(ganon_ctx *ctx, int32_t n_names, const char *names, const int64_t *name_off,
+                                     const int32_t *name_tid);
+GANON_API int ganon_ctx_sa_clips_counts(ganon_ctx *ctx, int64_t *masked, int64_t *ignored);
 /* --discover_sites (additive; the ABI version stays 5). A device site tally is the evidence tally of
  * include/ganon_host.h (ganon_site_tally_create: the rule, the byte per position) of ONE reference
  * sequence, in device memory: ganon_dtally_create uploads the sequence's upper-cased nt16 bases

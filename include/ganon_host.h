@@ -90,6 +90,25 @@ GANON_HOST_API int ganon_bam_open_ex(const char *path, int threads, const uint8_
 /* The bases the panel mask rewrote while this table was decoded on the host (0 for a table a region
  * decoder made: include/ganon.h ganon_ctx_known_sites_masked counts those). */
 GANON_HOST_API int64_t ganon_bam_known_sites_masked(const ganon_bam *bam);
+/* --mask_sa_clips (additive; csrc/ganon_sa_clips.h has the rule). ganon_sites_set_sa_clips
+ * gives a table the BAM header's sequence names, sorted bytewise and distinct (name i is
+ * names[name_off[i], name_off[i + 1]), BAM sequence id name_tid[i] < n_ref), and with on != 0 turns the
+ * rule on for every table and reader the handle is given to AFTER the call: a record that the panel mask
+ * does not skip and that has a soft clip (the first op after its leading H ops or the last before its
+ * trailing ones is S) has the entries of its first SA:Z tag walked in tag order, and every clipped base
+ * that an entry's M / = / X runs align to a listed position of the entry's sequence and that shows a
+ * listed ALT there (complemented when the entry's strand is not the record's) becomes the reference
+ * base (complemented back), its quality the table's quality as for the panel mask. An entry is used
+ * whole or not at all: six comma-separated fields, rname a header name, pos 1..2^31-1, strand + or -,
+ * a CIGAR of <1..2^28-1><MIDNSHP=X> runs whose query length (M I S = X H) is l_seq plus the record's own
+ * hard clips; any other entry is ignored and counted. A table without sites walks and counts nothing.
+ * The arrays are copied.
+ * ganon_bam_sa_clips_masked / ganon_bam_sa_entries_ignored: the clip bases rewritten and the entries
+ * ignored while this table was decoded on the host; they are no part of ganon_bam_known_sites_masked. */
+GANON_HOST_API int ganon_sites_set_sa_clips(ganon_sites *sites, int32_t n_names, const char *names, const int64_t *name_off,
+                                            const int32_t *name_tid, int on);
+GANON_HOST_API int64_t ganon_bam_sa_clips_masked(const ganon_bam *bam);
+GANON_HOST_API int64_t ganon_bam_sa_entries_ignored(const ganon_bam *bam);
 /* --discover_sites (additive). An evidence tally over the sequences of one run: n_seq sequences of the
  * upper-cased nt16 genome `nt16` (two bases per byte, a sequence's base 0 at nibble index nib_off[s], in
  * the high nibble when that index is even; nib_off[s] = -1: the sequence has no reference, nothing on
@@ -186,6 +205,10 @@ GANON_HOST_API int ganon_bam_reader_set_name_key(ganon_bam_reader *reader, const
  * turns it off. ganon_bam_reader_known_sites_masked: the bases this reader's host decodes rewrote. */
 GANON_HOST_API int ganon_bam_reader_set_known_sites(ganon_bam_reader *reader, const ganon_sites *sites);
 GANON_HOST_API int64_t ganon_bam_reader_known_sites_masked(const ganon_bam_reader *reader);
+/* --mask_sa_clips: what this reader's host decodes rewrote through SA tags, and the entries they ignored
+ * (a region decoder counts on its context: include/ganon.h ganon_ctx_sa_clips_counts). */
+GANON_HOST_API int64_t ganon_bam_reader_sa_clips_masked(const ganon_bam_reader *reader);
+GANON_HOST_API int64_t ganon_bam_reader_sa_entries_ignored(const ganon_bam_reader *reader);
 /* --discover_sites: the records of ganon_bam_reader_contig and ganon_bam_reader_region are tallied
  * from now on, inside the column pass on the reader's threads — the host path of a region read too
  * (a region decoder tallies on its context: ganon_ctx_set_site_tally). n_tid is the header's sequence

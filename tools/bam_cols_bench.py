@@ -18,6 +18,12 @@ positions per 1,000 bases of each sequence, REF the FASTA's base, one random ALT
 the kernel list, the host decoder masks inside its column pass, and the line reports the sites and the
 bases rewritten.
 
+--sa_clips FRAC (with --known_sites): a share FRAC of the one-op mapped records gets a trailing soft clip
+(the last third of the read) and an SA:Z entry that aligns the clip at a random position of the record's
+own sequence, and the table carries the header's names and the switch of --mask_sa_clips on both sides:
+k_bam_sa_clips joins the kernel list after k_bam_known_mask, and the line reports the clipped records, the
+clip bases rewritten and the entries ignored on both sides.
+
 --site_tally: the same with an evidence tally on both sides (--discover_sites): a device tally of the
 sequence most records lie on, as the tumor dataset — k_bam_site_tally joins the kernel list —, the host
 decoder tallying inside its column pass; the line reports the positions with evidence on both sides (they
@@ -68,6 +74,31 @@ def synthetic_panel(ref_path: str, ref_names, per_kb: float, seed: int = 1):
     return SitesTable(np.array(off, np.int64), np.concatenate(pos), np.concatenate(code))
 
 
+def with_sa_clips(recs: bytes, frac: float, ref_names, ref_lens, seed: int = 3):
+    """``recs`` (BAM records back to back) with a share ``frac`` of the mapped records whose CIGAR is one M op
+    rewritten to kM(L-k)S, k = 2L/3, and given an SA:Z entry (L-k bases at a random position of the record's
+    own sequence, same strand). Returns (the new records, how many were rewritten)."""
+    import struct
+    rng = np.random.default_rng(seed)
+    out, p, n, changed = [], 0, len(recs), 0
+    while p < n:
+        bs = struct.unpack_from("<i", recs, p)[0]
+        r = recs[p + 4:p + 4 + bs]
+        p += 4 + bs
+        tid, _, l_rn, _, _, ncig, flag, lseq = struct.unpack_from("<iiBBHHHi", r, 0)
+        if ncig == 1 and not (flag & 4) and 0 <= tid < len(ref_names) and lseq >= 3 and rng.random() < frac:
+            w = struct.unpack_from("<I", r, 32 + l_rn)[0]
+            if (w & 15) == 0 and (w >> 4) == lseq:
+                k = 2 * lseq // 3
+                at = int(rng.integers(1, max(2, int(ref_lens[tid]) - lseq)))
+                sa = f"SAZ{ref_names[tid]},{at},{'-' if flag & 16 else '+'},{k}S{lseq - k}M,60,0;".encode() + b"\x00"
+                cig = struct.pack("<II", k << 4, ((lseq - k) << 4) | 4)
+                r = r[:12] + struct.pack("<H", 2) + r[14:32 + l_rn] + cig + r[36 + l_rn:] + sa
+                changed += 1
+        out.append(struct.pack("<i", len(r)) + r)
+    return b"".join(out), changed
+
+
 def compact_20mb(g, n: int = 20_000_000, seed: int = 2) -> dict:
     """k_site_compact on a synthetic ``n``-base sequence: the evidence bytes uploaded as a host tally's."""
     from genomeanonymizer_amd import native
@@ -89,7 +120,7 @@ def compact_20mb(g, n: int = 20_000_000, seed: int = 2) -> dict:
 
 
 def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = None, sites_per_kb: float = 0.0,
-            site_tally: bool = False) -> dict:
+            site_tally: bool = False, sa_clips: float = 0.0) -> dict:
     import gzip
     from genomeanonymizer_amd import native
     from genomeanonymizer_amd.io.bam import ReadTable
@@ -101,6 +132,14 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
         d = gzip.decompress(open(paths["T"], "rb").read())
         p = first_record_offset(d)
         head, recs = d[:p], d[p:]
+        n_clipped = 0
+        if sa_clips > 0:
+            if sites_per_kb <= 0:
+                raise SystemExit("--sa_clips needs a panel: give --known_sites SITES_PER_KB too")
+            from genomeanonymizer_amd.io.bam import BamReader
+            hdr = BamReader(paths["T"], 1)
+            recs, n_clipped = with_sa_clips(recs, sa_clips, hdr.ref_names, hdr.ref_lens)
+            hdr.close()
         tiles = max(1, (mb << 20) // max(1, len(recs)))
         stream = np.frombuffer(head + recs * tiles, np.uint8)
         g = native.GpuInflater(0, min_blocks=1)
@@ -112,6 +151,9 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
             from genomeanonymizer_amd.io.bam import BamReader
             hdr = BamReader(paths["T"], 1)
             table = synthetic_panel(paths["ref"], hdr.ref_names, sites_per_kb)
+            if sa_clips > 0:
+                from genomeanonymizer_amd.known_sites import SitesTable
+                table = SitesTable(table.site_off, table.site_pos, table.site_code, table.quality, hdr.ref_names, True)
             hdr.close()
         g.set_known_sites(table)
         tally = dtally = None
@@ -142,6 +184,7 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
                 per[name] = per.get(name, 0.0) + float(arr[i].ms)
             runs.append((sum(per.values()), per, wall, fixes))
         dev_masked = g.known_sites_masked() // (reps + 1) if table is not None else 0
+        dev_sa = [c // (reps + 1) for c in g.sa_clips_counts()] if sa_clips > 0 else [0, 0]
         tally_out = None
         if site_tally:
             # the tumor evidence again as the normal dataset: every position with evidence is a site
@@ -185,6 +228,10 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
             "known_sites": None if table is None else {
                 "sites_per_kb": sites_per_kb, "sites": table.n, "table_bytes": int(5 * table.n + 8 * (table.n_ref + 1)),
                 "bases_rewritten_device": int(dev_masked), "bases_rewritten_host": int(t.known_masked)},
+            "sa_clips": None if sa_clips <= 0 else {
+                "frac": sa_clips, "records_clipped": int(n_clipped) * tiles, "clip_bases_rewritten_device": int(dev_sa[0]),
+                "clip_bases_rewritten_host": int(t.sa_masked), "entries_ignored_device": int(dev_sa[1]),
+                "entries_ignored_host": int(t.sa_ignored)},
             "site_tally": tally_out,
             "workload": f"configs[0] tumor BAM records tiled x{tiles} ({nr} records, 150 bp); device: the stream "
                         f"resident in HBM, kernels only (HIP events on the context's stream); call wall adds the H2D "
@@ -204,6 +251,9 @@ def main() -> None:
                     help="decode with a read-name key (GANON_READ_NAME_KEY as hex, else a fixed benchmark key)")
     ap.add_argument("--known_sites", type=float, default=0.0, metavar="SITES_PER_KB",
                     help="decode with a synthetic panel of this many sites per 1,000 bases (both sides)")
+    ap.add_argument("--sa_clips", type=float, default=0.0, metavar="FRAC",
+                    help="with --known_sites: this share of the records gets a trailing soft clip and an SA entry, and "
+                         "the decoders mask the clips along it (--mask_sa_clips)")
     ap.add_argument("--site_tally", action="store_true",
                     help="decode with an evidence tally (--discover_sites) on both sides, and time k_site_compact")
     args = ap.parse_args()
@@ -212,7 +262,7 @@ def main() -> None:
         from genomeanonymizer_amd import native
         v = os.environ.get(native.NAME_KEY_ENV)
         key = native.parse_name_key(v) if v is not None else BENCH_KEY
-    print(json.dumps(measure(args.mb, args.threads, args.reps, key, args.known_sites, args.site_tally)))
+    print(json.dumps(measure(args.mb, args.threads, args.reps, key, args.known_sites, args.site_tally, args.sa_clips)))
 
 
 if __name__ == "__main__":

@@ -27,6 +27,8 @@ Prints one JSON line with per-stage seconds, reads/s, bases/s and the process's 
                              # with "known_sites": the path
     GANON_DISCOVER_SITES=1   # --discover_sites: the pair's own shared SNV alleles masked: the same
                              # line with "discover_sites": true and the pre-pass's sites and seconds
+    GANON_MASK_SA_CLIPS=1    # --mask_sa_clips (with one of the two above): soft clips masked along their SA
+                             # alignments: the same line with "mask_sa_clips": true and the counts
     E2E_DISK_PROBE=1 ...     # also time 2 GiB of pwrite into OUTDIR (4 files at once, as the product
                              # writes; page cache, then with fsync): the box's write bandwidth
 """
@@ -223,6 +225,8 @@ def main():
                      "hash_read_names": _native.read_name_key_default() is not None,
                      "known_sites": os.environ.get("GANON_KNOWN_SITES") or None,
                      "discover_sites": os.environ.get("GANON_DISCOVER_SITES", "0") == "1",
+                     "mask_sa_clips": os.environ.get("GANON_MASK_SA_CLIPS", "0") == "1",
+                     "sa_clips_masked": best.get("sa_clips_masked"), "sa_entries_ignored": best.get("sa_entries_ignored"),
                      "cpus_available": len(os.sched_getaffinity(0)),
                      "output_bytes": sum(os.path.getsize(os.path.join(out, f"{x}_{mode}{s}{gz}"))
                                          for x in ("tumor", "normal") for s in (".1.fastq", ".2.fastq"))}

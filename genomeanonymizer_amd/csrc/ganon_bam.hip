@@ -346,6 +346,7 @@ struct ganon_dtally {
   int32_t *pos = nullptr;        // (after the compaction) n_sites positions and codes
   uint8_t *code = nullptr;
   int64_t n_sites = -1;
+  ganon_st::Rule rule;           // ganon_dtally_create_ex: the evidence filters and the mode (zero: none)
 };
 
 namespace {
@@ -700,6 +701,7 @@ struct StView {
   int64_t len;
   int32_t tid;          // the BAM sequence id whose records are evidence
   int32_t dataset;
+  ganon_st::Rule rule;  // (read by the filtered instantiation alone)
 };
 
 // ganon_st's store on the device: one relaxed agent-scope atomic OR on the aligned word that holds the
@@ -713,9 +715,12 @@ struct StStore {
 
 // One record with a long CIGAR, by one wave (every lane active): 64 ops at a time, their reference and
 // query starts from prefix sums (ks_incl_sum: the lengths in two 14-bit halves); a lane with an M / = /
-// X op tallies its op's bases (ganon_st::tally_span clips them to the read and the sequence).
+// X op tallies its op's bases (ganon_st::tally_span clips them to the read and the sequence). Filtered:
+// qual is the record's quality bytes, which each lane's q0 indexes as it does the bases.
+template <bool Filtered>
 __device__ __forceinline__ void st_tally_wave(const StView &T, int lane, int32_t pos, int32_t ncig, int32_t lseq,
-                                              const uint32_t *__restrict__ cig, const uint8_t *__restrict__ seq) {
+                                              const uint32_t *__restrict__ cig, const uint8_t *__restrict__ seq,
+                                              const uint8_t *__restrict__ qual) {
   const ganon_st::Ref R{T.ref, 0, T.len};
   StStore st{T.words};
   int64_t r = pos, q = 0;
@@ -727,7 +732,9 @@ __device__ __forceinline__ void st_tally_wave(const StView &T, int lane, int32_t
     const uint32_t rl = (m || op == 2 || op == 3) ? len : 0u, ql = (m || op == 1 || op == 4) ? len : 0u;
     int64_t rt, qt;
     const int64_t r0 = r + ks_incl_sum(rl, rt) - rl, q0 = q + ks_incl_sum(ql, qt) - ql;
-    if (m && len) ganon_st::tally_span(R, seq, lseq, r0, q0, (int64_t)len, 4 * T.dataset, st);
+    if (m && len)
+      ganon_st::tally_span<Filtered>(R, seq, qual, Filtered ? T.rule.min_base_quality : 0, lseq, r0, q0, (int64_t)len,
+                                     4 * T.dataset, st);
     r += rt;
     q += qt;
   }
@@ -739,7 +746,11 @@ __device__ __forceinline__ void st_tally_wave(const StView &T, int lane, int32_t
 // nibble only inside a word that differs: mismatches are about 0.1-1 % of the bases, the atomic ORs are
 // rare. Records with more than kKsLongOps ops are listed in LDS and taken a wave each after the
 // barrier (st_tally_wave), as k_bam_known_mask does and for the same reason: one thread on a
-// thousand-op CIGAR would hold its wave.
+// thousand-op CIGAR would hold its wave. Filtered (a rule with an evidence filter; false is the kernel
+// without one, which reads neither mapq nor a quality byte): a record also leaves when its mapq is below
+// the rule's or its flag has an excluded bit, and a differing base counts only with its own quality byte
+// at or above the rule's: a byte load per mismatch.
+template <bool Filtered>
 __global__ void __launch_bounds__(kBamThreads) k_bam_site_tally(ganon_bam_cols V, int64_t nr, StView T) {
   __shared__ int s_long[kBamThreads];
   __shared__ int s_nlong;
@@ -749,13 +760,15 @@ __global__ void __launch_bounds__(kBamThreads) k_bam_site_tally(ganon_bam_cols V
   const int64_t i = i0 + threadIdx.x;
   if (i < nr && V.tid[i] == T.tid) {
     const int32_t flag = V.flag[i], ncig = V.n_cigar[i], lseq = V.l_seq[i];
-    if (!(flag & 4) && ncig > 0 && lseq > 0) {
+    if (!(flag & 4) && ncig > 0 && lseq > 0 && (!Filtered || ganon_st::passes(T.rule, (uint32_t)flag, V.mapq[i]))) {
       if (ncig > kKsLongOps) {
         s_long[atomicAdd(&s_nlong, 1)] = (int)threadIdx.x;
       } else {
         const ganon_st::Ref R{T.ref, 0, T.len};
         StStore st{T.words};
-        ganon_st::tally_record(R, V.pos[i], ncig, lseq, V.cigar + V.cig_off[i], V.seq + V.seq_off[i], T.dataset, st);
+        ganon_st::tally_record<Filtered>(R, V.pos[i], ncig, lseq, V.cigar + V.cig_off[i], V.seq + V.seq_off[i],
+                                         Filtered ? V.qual + V.qual_off[i] : nullptr, Filtered ? T.rule.min_base_quality : 0,
+                                         T.dataset, st);
       }
     }
   }
@@ -763,17 +776,19 @@ __global__ void __launch_bounds__(kBamThreads) k_bam_site_tally(ganon_bam_cols V
   const int nlong = s_nlong, lane = threadIdx.x & 63;
   for (int k = threadIdx.x >> 6; k < nlong; k += kBamThreads / 64) {   // (wave-uniform)
     const int64_t g = i0 + s_long[k];
-    st_tally_wave(T, lane, V.pos[g], V.n_cigar[g], V.l_seq[g], V.cigar + V.cig_off[g], V.seq + V.seq_off[g]);
+    st_tally_wave<Filtered>(T, lane, V.pos[g], V.n_cigar[g], V.l_seq[g], V.cigar + V.cig_off[g], V.seq + V.seq_off[g],
+                            Filtered ? V.qual + V.qual_off[g] : nullptr);
   }
 }
 
 constexpr int kSiteTile = 8 * kBamThreads;   // positions per workgroup of k_site_compact: eight a thread
 
 // The sites of a tally: a thread takes eight positions (two dwords of tally bytes, OR-ed with the host
-// tally's where the host side touched the sequence), alt = low & high nibble per byte. Write false:
+// tally's where the host side touched the sequence), alt = low & high nibble per byte, or with Normal
+// (the rule's mode `normal`) the high nibble alone: the low one is not consulted. Write false:
 // the tile's site count to count[tile]. Write true: the sites at base[tile] (the scanned counts) plus
 // the block's exclusive prefix, in position order, the reference nibble from the sequence's nt16.
-template <bool Write>
+template <bool Write, bool Normal>
 __global__ void __launch_bounds__(kBamThreads) k_site_compact(const uint32_t *__restrict__ words,
                                                               const uint32_t *__restrict__ host_words,
                                                               const uint8_t *__restrict__ ref, int64_t *__restrict__ count,
@@ -787,7 +802,7 @@ __global__ void __launch_bounds__(kBamThreads) k_site_compact(const uint32_t *__
     w.x |= h.x;
     w.y |= h.y;
   }
-  const uint32_t a0 = w.x & (w.x >> 4) & 0x0F0F0F0Fu, a1 = w.y & (w.y >> 4) & 0x0F0F0F0Fu;
+  const uint32_t a0 = (Normal ? ~0u : w.x) & (w.x >> 4) & 0x0F0F0F0Fu, a1 = (Normal ? ~0u : w.y) & (w.y >> 4) & 0x0F0F0F0Fu;
   int cnt = 0;
   for (int j = 0; j < 4; ++j) cnt += ((a0 >> (8 * j)) & 15u ? 1 : 0) + ((a1 >> (8 * j)) & 15u ? 1 : 0);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1093,10 +1108,13 @@ int columns(ganon_ctx *ctx, const uint8_t *d, int64_t p, int64_t n, ganon_bam_dc
   }
   if (nr && ctx->st_tally) {   // --discover_sites: the evidence of the columns just written
     const ganon_dtally *D = ctx->st_tally;
-    const StView T{D->ref, D->words, D->len, ctx->st_tid, ctx->st_dataset};
+    const StView T{D->ref, D->words, D->len, ctx->st_tid, ctx->st_dataset, D->rule};
     {
       ganon_detail::KernelScope ks(ctx, "k_bam_site_tally");
-      hipLaunchKernelGGL(k_bam_site_tally, dim3(grid_of(nr)), dim3(kBamThreads), 0, s, V, nr, T);
+      if (ganon_st::filtered(D->rule))
+        hipLaunchKernelGGL(k_bam_site_tally<true>, dim3(grid_of(nr)), dim3(kBamThreads), 0, s, V, nr, T);
+      else
+        hipLaunchKernelGGL(k_bam_site_tally<false>, dim3(grid_of(nr)), dim3(kBamThreads), 0, s, V, nr, T);
     }
     if ((rc = check_launch(ctx, "k_bam_site_tally"))) return rc;
   }
@@ -1338,13 +1356,19 @@ static void dtally_release(ganon_dtally *D) {
   delete D;
 }
 
-GANON_API int ganon_dtally_create(ganon_ctx *ctx, const uint8_t *ref_nt16, int64_t len, ganon_dtally **out) {
+GANON_API int ganon_dtally_create_ex(ganon_ctx *ctx, const uint8_t *ref_nt16, int64_t len, int32_t min_base_quality,
+                                     int32_t min_mapq, uint32_t exclude_flags, int32_t mode, ganon_dtally **out) {
   if (!ctx || !out || len < 0 || len > INT32_MAX || (len > 0 && !ref_nt16))
     return fail(ctx, GANON_E_ARG, "ganon_dtally_create: bad arguments");
   *out = nullptr;
+  const ganon_st::Rule rule{min_base_quality, min_mapq, exclude_flags, mode};
+  if (!ganon_st::rule_valid(rule))
+    return fail(ctx, GANON_E_ARG,
+                "ganon_dtally_create_ex: base quality 0..93, mapq 0..255, flags 0..65535, mode 0 (both) or 1 (normal)");
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GANON_E_DEVICE, "hipSetDevice failed");
   auto *D = new ganon_dtally();
   D->len = len;
+  D->rule = rule;
   D->padded = std::max<int64_t>(1, (len + kSiteTile - 1) / kSiteTile) * kSiteTile;
   hipStream_t s = ctx->stream;
   if (hipMalloc(reinterpret_cast<void **>(&D->ref), (size_t)D->padded / 2) != hipSuccess ||
@@ -1359,6 +1383,10 @@ GANON_API int ganon_dtally_create(ganon_ctx *ctx, const uint8_t *ref_nt16, int64
   }
   *out = D;
   return GANON_OK;
+}
+
+GANON_API int ganon_dtally_create(ganon_ctx *ctx, const uint8_t *ref_nt16, int64_t len, ganon_dtally **out) {
+  return ganon_dtally_create_ex(ctx, ref_nt16, len, 0, 0, 0u, ganon_st::kBoth, out);
 }
 
 GANON_API int ganon_ctx_set_site_tally(ganon_ctx *ctx, ganon_dtally *tally, int32_t dataset, int32_t tid) {
@@ -1386,6 +1414,7 @@ GANON_API int ganon_dtally_compact(ganon_ctx *ctx, ganon_dtally *D, const uint8_
     ctx->recs.clear();
   }
   const int64_t tiles = D->padded / kSiteTile;
+  const bool normal = D->rule.mode == ganon_st::kNormal;
   std::vector<std::pair<void *, size_t>> tmp;
   auto dalloc = [&](size_t bytes) -> void * {
     void *q = nullptr;
@@ -1421,8 +1450,12 @@ GANON_API int ganon_dtally_compact(ganon_ctx *ctx, ganon_dtally *D, const uint8_
   HIP_OR_FAIL(hipMemsetAsync(count + tiles, 0, 8, s));
   {
     ganon_detail::KernelScope ks(ctx, "k_site_compact");
-    hipLaunchKernelGGL(k_site_compact<false>, dim3((unsigned)tiles), dim3(kBamThreads), 0, s, D->words, hw, D->ref, count,
-                       base, nullptr, nullptr);
+    if (normal)
+      hipLaunchKernelGGL((k_site_compact<false, true>), dim3((unsigned)tiles), dim3(kBamThreads), 0, s, D->words, hw, D->ref,
+                         count, base, nullptr, nullptr);
+    else
+      hipLaunchKernelGGL((k_site_compact<false, false>), dim3((unsigned)tiles), dim3(kBamThreads), 0, s, D->words, hw, D->ref,
+                         count, base, nullptr, nullptr);
   }
   if ((rc = check_launch(ctx, "k_site_compact"))) return rc;
   {
@@ -1438,8 +1471,12 @@ GANON_API int ganon_dtally_compact(ganon_ctx *ctx, ganon_dtally *D, const uint8_
     HIP_OR_FAIL(hipMalloc(reinterpret_cast<void **>(&D->code), (size_t)total));
     {
       ganon_detail::KernelScope ks(ctx, "k_site_compact");
-      hipLaunchKernelGGL(k_site_compact<true>, dim3((unsigned)tiles), dim3(kBamThreads), 0, s, D->words, hw, D->ref, count,
-                         base, D->pos, D->code);
+      if (normal)
+        hipLaunchKernelGGL((k_site_compact<true, true>), dim3((unsigned)tiles), dim3(kBamThreads), 0, s, D->words, hw, D->ref,
+                           count, base, D->pos, D->code);
+      else
+        hipLaunchKernelGGL((k_site_compact<true, false>), dim3((unsigned)tiles), dim3(kBamThreads), 0, s, D->words, hw, D->ref,
+                           count, base, D->pos, D->code);
     }
     if ((rc = check_launch(ctx, "k_site_compact"))) return rc;
   }

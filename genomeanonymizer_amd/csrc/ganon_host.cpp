@@ -226,6 +226,7 @@ static const ganon_sa::Names *sa_of(const ganon_sites *s) { return s ? s->data->
 struct TallyData {
   const uint8_t *nt16 = nullptr;   // the caller's packed genome (kept alive by the caller)
   std::vector<int64_t> off, len;   // per sequence: nibble offset in nt16 (-1: not in the FASTA), bases
+  ganon_st::Rule rule;             // the evidence filters and the mode (ganon_site_tally_create_ex; zero: none)
   std::vector<std::atomic<uint8_t *>> bytes;
   std::atomic<bool> failed{false};   // an array could not be allocated
   std::mutex mu;
@@ -506,13 +507,19 @@ int records_to_columns(const uint8_t *d, int64_t p, int64_t n, ganon_bam *bam, i
       bam->aux_off[i] = o_aux[i];
       bam->aux_len[i] = (int32_t)(bs - q);
       copy_bytes(bam->aux.data() + o_aux[i], r + q, (size_t)(bs - q));
-      if (tally && !ganon_st::skips((int32_t)tally->slot_of_tid.size(), rtid, rflag, ncig, lseq)) {
+      if (tally && !ganon_st::skips((int32_t)tally->slot_of_tid.size(), rtid, rflag, ncig, lseq) &&
+          ganon_st::passes(tally->data->rule, rflag, rmapq)) {
         const int32_t slot = tally->slot_of_tid[(size_t)rtid];
         TallyData *T = tally->data.get();
         if (slot >= 0 && T->off[(size_t)slot] >= 0) {
           const ganon_st::Ref R{T->nt16, T->off[(size_t)slot], T->len[(size_t)slot]};
           TallyStore st{T, slot, nullptr};
-          ganon_st::tally_record(R, rpos, ncig, lseq, cg, bam->seq.data() + o_seq[i], tally->dataset, st);
+          const int min_bq = T->rule.min_base_quality;
+          if (min_bq > 0)
+            ganon_st::tally_record<true>(R, rpos, ncig, lseq, cg, bam->seq.data() + o_seq[i], bam->qual.data() + o_qual[i], min_bq,
+                                         tally->dataset, st);
+          else
+            ganon_st::tally_record<false>(R, rpos, ncig, lseq, cg, bam->seq.data() + o_seq[i], nullptr, 0, tally->dataset, st);
         }
       }
       if (sites)
@@ -711,11 +718,15 @@ GANON_HOST_API int ganon_sites_set_sa_clips(ganon_sites *s, int32_t n_names, con
 GANON_HOST_API int64_t ganon_bam_sa_clips_masked(const ganon_bam *b) { return b ? b->sa_masked : 0; }
 GANON_HOST_API int64_t ganon_bam_sa_entries_ignored(const ganon_bam *b) { return b ? b->sa_ignored : 0; }
 
-GANON_HOST_API int ganon_site_tally_create(int32_t n_seq, const uint8_t *nt16, const int64_t *nib_off, const int64_t *len,
-                                           ganon_site_tally **out) {
+GANON_HOST_API int ganon_site_tally_create_ex(int32_t n_seq, const uint8_t *nt16, const int64_t *nib_off, const int64_t *len,
+                                              int32_t min_base_quality, int32_t min_mapq, uint32_t exclude_flags, int32_t mode,
+                                              ganon_site_tally **out) {
   if (!out) return set_err("null argument");
   *out = nullptr;
   if (n_seq < 0 || (n_seq > 0 && (!nib_off || !len))) return set_err("ganon_site_tally_create: bad arguments");
+  const ganon_st::Rule rule{min_base_quality, min_mapq, exclude_flags, mode};
+  if (!ganon_st::rule_valid(rule))
+    return set_err("ganon_site_tally_create_ex: base quality 0..93, mapq 0..255, flags 0..65535, mode 0 (both) or 1 (normal)");
   for (int32_t s = 0; s < n_seq; ++s)
     if (len[s] < 0 || len[s] > INT32_MAX || nib_off[s] < -1 || (nib_off[s] >= 0 && len[s] > 0 && !nt16))
       return set_err("ganon_site_tally_create: a sequence's length is 0..2^31-1, its nibble offset >= 0 or -1");
@@ -724,11 +735,17 @@ GANON_HOST_API int ganon_site_tally_create(int32_t n_seq, const uint8_t *nt16, c
     d->nt16 = nt16;
     d->off.assign(nib_off, nib_off + n_seq);
     d->len.assign(len, len + n_seq);
+    d->rule = rule;
     *out = new ganon_site_tally{std::move(d)};
     return 0;
   } catch (const std::bad_alloc &) {
     return set_err("out of memory making a site tally");
   }
+}
+
+GANON_HOST_API int ganon_site_tally_create(int32_t n_seq, const uint8_t *nt16, const int64_t *nib_off, const int64_t *len,
+                                           ganon_site_tally **out) {
+  return ganon_site_tally_create_ex(n_seq, nt16, nib_off, len, 0, 0, 0u, ganon_st::kBoth, out);
 }
 
 GANON_HOST_API void ganon_site_tally_destroy(ganon_site_tally *t) { delete t; }
@@ -744,8 +761,8 @@ GANON_HOST_API int64_t ganon_site_tally_count(const ganon_site_tally *t, int32_t
   const TallyData &T = *t->data;
   const uint8_t *b = T.bytes[(size_t)seq].load(std::memory_order_acquire);
   if (!b) return 0;
-  return ganon_st::compact(ganon_st::Ref{T.nt16, T.off[(size_t)seq], T.len[(size_t)seq]}, b, T.len[(size_t)seq], nullptr,
-                           nullptr);
+  return ganon_st::compact(ganon_st::Ref{T.nt16, T.off[(size_t)seq], T.len[(size_t)seq]}, b, T.len[(size_t)seq],
+                           T.rule.mode, nullptr, nullptr);
 }
 
 GANON_HOST_API int64_t ganon_site_tally_finish(ganon_site_tally *t, int32_t seq, int32_t *pos, uint8_t *code, int64_t cap) {
@@ -758,12 +775,12 @@ GANON_HOST_API int64_t ganon_site_tally_finish(ganon_site_tally *t, int32_t seq,
   int64_t n = 0;
   if (b) {
     const ganon_st::Ref R{T.nt16, T.off[(size_t)seq], T.len[(size_t)seq]};
-    n = ganon_st::compact(R, b, T.len[(size_t)seq], nullptr, nullptr);
+    n = ganon_st::compact(R, b, T.len[(size_t)seq], T.rule.mode, nullptr, nullptr);
     if (n > cap || (n > 0 && (!pos || !code))) {
       set_err("ganon_site_tally_finish: the arrays are too small (ganon_site_tally_count gives the number)");
       return -1;
     }
-    ganon_st::compact(R, b, T.len[(size_t)seq], pos, code);
+    ganon_st::compact(R, b, T.len[(size_t)seq], T.rule.mode, pos, code);
   }
   T.release(seq);
   return n;

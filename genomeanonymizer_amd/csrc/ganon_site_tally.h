@@ -11,6 +11,14 @@
 // site when alt = low & high is non-zero, its code ref_nt16 << 4 | alt (ganon_known_sites.h's table).
 // Bits are only ever OR-ed in: the tally depends neither on the order of the records nor on a record
 // being tallied twice.
+//
+// Rule (the evidence filters and the mode): a record whose mapq is below min_mapq or whose flag has a
+// bit of exclude_flags gives no evidence; a base gives evidence only when its own quality byte, compared
+// unsigned, is >= min_base_quality (a record without qualities stores 0xFF and passes: no special
+// case). The filters decide which bases may set a bit, nothing else: the bits are still only OR-ed in.
+// Mode kBoth reads the byte as above; under kNormal position r is a site when alt = high nibble is
+// non-zero and the tumor's nibble is not consulted. Evidence never holds the reference's base, so the
+// code stays a valid table code in both modes. The zero Rule is the unfiltered intersection.
 #ifndef GANON_SITE_TALLY_H
 #define GANON_SITE_TALLY_H
 
@@ -32,6 +40,26 @@ struct Ref {
   int64_t off = -1;
   int64_t len = 0;
 };
+
+enum Mode : int32_t { kBoth = 0, kNormal = 1 };
+
+struct Rule {
+  int32_t min_base_quality = 0;   // 0..93
+  int32_t min_mapq = 0;           // 0..255
+  uint32_t exclude_flags = 0;     // 0..65535
+  int32_t mode = kBoth;
+};
+
+ST_FN bool rule_valid(const Rule &u) {
+  return u.min_base_quality >= 0 && u.min_base_quality <= 93 && u.min_mapq >= 0 && u.min_mapq <= 255 &&
+         u.exclude_flags <= 65535u && (u.mode == kBoth || u.mode == kNormal);
+}
+
+// Is any evidence filter set? (the mode is no filter: it is how the bytes are read)
+ST_FN bool filtered(const Rule &u) { return u.min_base_quality > 0 || u.min_mapq > 0 || u.exclude_flags != 0; }
+
+// May a record that `skips` leaves in give evidence under the rule's record filters?
+ST_FN bool passes(const Rule &u, uint32_t flag, int32_t mapq) { return mapq >= u.min_mapq && !(flag & u.exclude_flags); }
 
 // Does the rule skip the record whole? (ganon_ks::skips: the records the mask later leaves alone)
 ST_FN bool skips(int32_t n_ref, int32_t tid, uint32_t flag, int32_t ncig, int32_t lseq) {
@@ -63,10 +91,12 @@ ST_FN uint32_t nib8(const uint8_t *p, int64_t x, int cnt) {
 
 // The bases of one M / = / X op: query [q, q + len) against reference [r, r + len), clipped to the
 // read (q < lseq) and the sequence (0 <= r < R.len). Eight bases a step: read nibbles XOR reference
-// nibbles, nibble by nibble only inside a word that differs. store(position, bits) ORs.
-template <class Store>
-ST_FN void tally_span(const Ref &R, const uint8_t *seq, int32_t lseq, int64_t r, int64_t q, int64_t len, int shift,
-                      Store &store) {
+// nibbles, nibble by nibble only inside a word that differs. store(position, bits) ORs. Qual: a
+// differing base is evidence only when qual[its query index] >= min_bq; the quality bytes are read at
+// mismatches alone (qual is the record's, indexed like seq: the clip below moves both).
+template <bool Qual, class Store>
+ST_FN void tally_span(const Ref &R, const uint8_t *seq, const uint8_t *qual, int min_bq, int32_t lseq, int64_t r, int64_t q,
+                      int64_t len, int shift, Store &store) {
   if (r < 0) {   // (a record placed before the sequence's start)
     q -= r;
     len += r;
@@ -84,24 +114,27 @@ ST_FN void tally_span(const Ref &R, const uint8_t *seq, int32_t lseq, int64_t r,
       const int s = 28 - 4 * j;
       if (!((x >> s) & 15u)) continue;
       const int b = (int)((rd >> s) & 15u), f = (int)((rf >> s) & 15u);
-      if (one_base(b) && one_base(f)) store(r + k + j, (uint8_t)(b << shift));
+      if (!(one_base(b) && one_base(f))) continue;
+      if (Qual && (int)qual[q + k + j] < min_bq) continue;
+      store(r + k + j, (uint8_t)(b << shift));
     }
   }
 }
 
 // One record, by one thread: its CIGAR walked from pos (M = X advance both, I S the query, D N the
 // reference, H P neither). dataset 0 (tumor) ORs into the low nibbles, 1 (normal) into the high ones.
-// The caller has checked `skips` and that R.off >= 0.
-template <class Store>
+// The caller has checked `skips`, `passes` and that R.off >= 0. Qual: as tally_span (qual: the
+// record's lseq quality bytes, not read otherwise).
+template <bool Qual, class Store>
 ST_FN void tally_record(const Ref &R, int32_t pos, int32_t ncig, int32_t lseq, const uint32_t *cig, const uint8_t *seq,
-                        int dataset, Store &store) {
+                        const uint8_t *qual, int min_bq, int dataset, Store &store) {
   int64_t r = pos, q = 0;
   for (int k = 0; k < ncig && q < lseq && r < R.len; ++k) {
     const uint32_t w = cig[k];
     const int op = (int)(w & 15u);
     const int64_t len = w >> 4;
     if (op == 0 || op == 7 || op == 8) {
-      tally_span(R, seq, lseq, r, q, len, 4 * dataset, store);
+      tally_span<Qual>(R, seq, qual, min_bq, lseq, r, q, len, 4 * dataset, store);
       r += len;
       q += len;
     } else if (op == 1 || op == 4) {
@@ -113,11 +146,12 @@ ST_FN void tally_record(const Ref &R, int32_t pos, int32_t ncig, int32_t lseq, c
 }
 
 // (pos, code) of the sites of one sequence's tally bytes, in position order; returns their number
-// (pos / code null: the count alone). The reference nibble comes from R.
-ST_FN int64_t compact(const Ref &R, const uint8_t *bytes, int64_t len, int32_t *pos, uint8_t *code) {
+// (pos / code null: the count alone). The reference nibble comes from R. mode kBoth: alt = low & high
+// nibble; kNormal: alt = the high nibble alone.
+ST_FN int64_t compact(const Ref &R, const uint8_t *bytes, int64_t len, int32_t mode, int32_t *pos, uint8_t *code) {
   int64_t n = 0;
   for (int64_t r = 0; r < len; ++r) {
-    const int alt = bytes[r] & (bytes[r] >> 4) & 15;
+    const int alt = (mode == kNormal ? 15 : bytes[r]) & (bytes[r] >> 4) & 15;
     if (!alt) continue;
     if (pos) {
       const int64_t x = R.off + r;

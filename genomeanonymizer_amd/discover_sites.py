@@ -10,6 +10,24 @@ table and no name key and tallies, per reference position, the alleles each data
 the positions where the two sets intersect become a ``known_sites.Panel``, and everything after that is
 ``--known_sites``: the pair's own SNV calls are left out, the readers mask where they decode.
 
+Evidence filters and the rule (``SiteRule``; the four options below need ``--discover_sites``):
+
+* ``--discover_min_base_quality Q`` (0..93): a base is evidence only when its own quality byte is >= Q;
+  a record that stores no qualities has 0xFF everywhere and passes.
+* ``--discover_min_mapq M`` (0..255) and ``--discover_exclude_flags F`` (0..65535, decimal or 0x...): a
+  record with mapq < M, or with a flag bit of F, gives no evidence.
+* ``--discover_rule both|normal``: ``both`` is the intersection above. Under ``normal`` an allele a
+  normal read shows is a site whatever the tumor shows: where the tumor lost a haplotype (loss of
+  heterozygosity, tens of megabases in many tumors) or has a coverage gap, the intersection is empty and
+  the donor's heterozygous alleles would reach the normal's FASTQ. The evidence that an allele is germline
+  is the normal's; the pair's own SNV calls, which the product keeps, are left out of the table anyway.
+  Every sequencing error of the normal is a site under ``normal``: use it with the filters.
+
+The filters apply to both datasets alike and decide which bases are evidence, nothing else: the mask
+itself is not filtered and rewrites every base that shows a site's ALT, whatever its quality or its
+record's mapq (§4i). All four have environment defaults (``GANON_DISCOVER_MIN_BASE_QUALITY``,
+``GANON_DISCOVER_MIN_MAPQ``, ``GANON_DISCOVER_EXCLUDE_FLAGS``, ``GANON_DISCOVER_RULE``), read once per pair.
+
 * ``discover(tumor_bam, normal_bam, fasta, ...)`` is the pre-pass; with several ranks each takes the
   sequences ``i % world`` and the lists are exchanged over a side gloo group.
 * ``merge(a, b)`` ORs two panels position by position.
@@ -19,9 +37,12 @@ the positions where the two sets intersect become a ``known_sites.Panel``, and e
 The discovered list is the donor's germline SNV list: it is never logged and never written; the log
 lines give counts only.
 
-Limits: indels are not discovered; there are no depth, quality or strand thresholds (one tumor and one
-normal read are enough, as in the rule); a supplementary record's bases in the primary's soft clip are
-not masked (§4i); ``reference_adapter`` does not use it; the pre-pass decodes every record a second time.
+Limits: indels are not discovered; base-quality, mapq and flag filters exist, depth, read-count, VAF and
+strand thresholds do not (one passing base per dataset is enough): the tally is a byte of OR-ed bits per
+position, which is what makes records tallied twice — shared by two region reads, by a window decoded
+again, by the host and the device half — harmless, and a count would not be; a supplementary record's
+bases in the primary's soft clip are not masked (§4i); ``reference_adapter`` does not use it; the
+pre-pass decodes every record a second time.
 """
 from __future__ import annotations
 
@@ -39,6 +60,12 @@ from .known_sites import PairPanel, Panel, mask_sa_clips_default, panel_default
 log = logging.getLogger("genomeanonymizer_amd")
 
 ENV = "GANON_DISCOVER_SITES"
+MIN_BASE_QUALITY_ENV = "GANON_DISCOVER_MIN_BASE_QUALITY"
+MIN_MAPQ_ENV = "GANON_DISCOVER_MIN_MAPQ"
+EXCLUDE_FLAGS_ENV = "GANON_DISCOVER_EXCLUDE_FLAGS"
+RULE_ENV = "GANON_DISCOVER_RULE"
+RULE_ENVS = (MIN_BASE_QUALITY_ENV, MIN_MAPQ_ENV, EXCLUDE_FLAGS_ENV, RULE_ENV)
+SiteRule = native.SiteRule
 REGION_ENV = "GANON_DISCOVER_BP"    # bases per region read of the pre-pass on indexed BAMs (default 8 Mb)
 
 
@@ -48,13 +75,35 @@ def default_on() -> bool:
     return os.environ.get(ENV, "0") == "1"
 
 
+def parse_flags(text: str) -> int:
+    """``--discover_exclude_flags``: decimal or ``0x...``."""
+    t = str(text).strip()
+    return int(t, 16) if t.lower().startswith("0x") else int(t, 10)
+
+
+def rule_default() -> SiteRule:
+    """The rule of the four environment defaults (``--discover_min_base_quality``, ``--discover_min_mapq``,
+    ``--discover_exclude_flags``, ``--discover_rule``), checked; ValueError names the option at fault."""
+    def num(env, option, parse=int):
+        v = os.environ.get(env, "") or "0"
+        try:
+            return parse(v)
+        except ValueError:
+            raise ValueError(f"{option} ({env}): not a number: {v!r}") from None
+    return SiteRule(num(MIN_BASE_QUALITY_ENV, "--discover_min_base_quality"), num(MIN_MAPQ_ENV, "--discover_min_mapq"),
+                    num(EXCLUDE_FLAGS_ENV, "--discover_exclude_flags", parse_flags),
+                    os.environ.get(RULE_ENV, "") or "both").checked()
+
+
 class HostTally:
     """The host library's evidence tally (``ganon_site_tally``, include/ganon_host.h) over named
     sequences of a packed nt16 genome: ``names[i]`` has ``lengths[i]`` bases from nibble ``nib_off[i]`` of
     ``packed`` on (-1: no reference). Readers take it with a dataset (0 tumor, 1 normal):
-    ``BamReader.set_site_tally``, ``ReadTable(site_tally=)``."""
+    ``BamReader.set_site_tally``, ``ReadTable(site_tally=)``. ``rule``: a SiteRule the readers and
+    ``finish`` read from the tally (None: no filter, mode "both")."""
 
-    def __init__(self, names: Sequence[str], packed: np.ndarray, nib_off: Sequence[int], lengths: Sequence[int]):
+    def __init__(self, names: Sequence[str], packed: np.ndarray, nib_off: Sequence[int], lengths: Sequence[int],
+                 rule: Optional[SiteRule] = None):
         self.names = list(names)
         self.index = {}
         for i, n in enumerate(self.names):
@@ -64,17 +113,18 @@ class HostTally:
         self.lengths = np.ascontiguousarray(lengths, np.int64)
         lib = native.host_lib()
         h = C.c_void_p()
-        if lib.ganon_site_tally_create(len(self.names), native._ptr(self.packed, native._u8p),
-                                       native._ptr(self.nib_off, native._i64p), native._ptr(self.lengths, native._i64p),
-                                       C.byref(h)) != 0:
+        self.rule = (rule or SiteRule()).checked()
+        if lib.ganon_site_tally_create_ex(len(self.names), native._ptr(self.packed, native._u8p),
+                                          native._ptr(self.nib_off, native._i64p), native._ptr(self.lengths, native._i64p),
+                                          *self.rule.c_args(), C.byref(h)) != 0:
             raise native.GanonError(lib.ganon_host_last_error().decode())
         self._h = h
 
     @classmethod
-    def of_fasta(cls, fasta) -> "HostTally":
+    def of_fasta(cls, fasta, rule: Optional[SiteRule] = None) -> "HostTally":
         packed, off = fasta.packed()
         names = list(fasta.references)
-        return cls(names, packed, [off[n] for n in names], list(fasta.lengths))
+        return cls(names, packed, [off[n] for n in names], list(fasta.lengths), rule)
 
     @property
     def handle(self):
@@ -162,9 +212,11 @@ def _pass_one(reader, tid: int, region_bp: int) -> None:
 
 
 def discover(tumor_bam: str, normal_bam: str, fasta, threads: int = 8, inflater=None, dist=None,
-             window_bytes: int = 0, stats: Optional[dict] = None) -> Panel:
+             window_bytes: int = 0, stats: Optional[dict] = None, rule: Optional[SiteRule] = None) -> Panel:
     """The pre-pass: the positions where a tumor read and a normal read show one allele other than the
-    reference's, as a Panel (contig name -> sorted positions, codes ref_nt16 << 4 | alt). ``inflater``: a
+    reference's — under ``rule`` (None: the environment defaults, ``rule_default``) with its evidence
+    filters, and with mode "normal" the positions where a normal read shows one —, as a Panel (contig
+    name -> sorted positions, codes ref_nt16 << 4 | alt). ``inflater``: a
     native.GpuInflater whose context inflates and, in region reads, decodes and tallies on the device
     (None: the host decoder). ``dist``: the initialised torch.distributed world; every rank returns the
     same Panel."""
@@ -173,7 +225,8 @@ def discover(tumor_bam: str, normal_bam: str, fasta, threads: int = 8, inflater=
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
     region_bp = int(os.environ.get(REGION_ENV, "8000000") or 0)
-    tally = HostTally.of_fasta(fasta)
+    rule = (rule_default() if rule is None else rule).checked()
+    tally = HostTally.of_fasta(fasta, rule)
     readers = [BamReader(p, threads, window_bytes, inflater=inflater) for p in (tumor_bam, normal_bam)]
     on_device = inflater is not None and hasattr(inflater, "set_site_tally")
     contigs: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
@@ -187,7 +240,7 @@ def discover(tumor_bam: str, normal_bam: str, fasta, threads: int = 8, inflater=
             tids = [int(np.nonzero(m == i)[0][0]) if (m == i).any() else -1 for m in maps]
             if max(tids) < 0:
                 continue
-            dt = native.DeviceTally(inflater, tally.reference_of(i), int(tally.lengths[i])) if on_device else None
+            dt = native.DeviceTally(inflater, tally.reference_of(i), int(tally.lengths[i]), rule) if on_device else None
             try:
                 for d, r in enumerate(readers):
                     if tids[d] < 0:
@@ -227,8 +280,10 @@ def discover(tumor_bam: str, normal_bam: str, fasta, threads: int = 8, inflater=
     out = {"sites": sum(len(p) for p, _ in contigs.values()), "prepass_s": round(time.time() - t0, 3)}
     if stats is not None:
         stats.update(out)
-    log.info("discovered sites: %d positions where tumor and normal reads show one allele, pre-pass %.3f s", out["sites"],
-             out["prepass_s"])
+    log.info("discovered sites: %d positions where %s one allele (min base quality %d, min mapq %d, excluded flags 0x%x, "
+             "rule %s), pre-pass %.3f s", out["sites"],
+             "normal reads show" if rule.mode == "normal" else "tumor and normal reads show", rule.min_base_quality,
+             rule.min_mapq, rule.exclude_flags, rule.mode, out["prepass_s"])
     return Panel("<discovered>", contigs, out)
 
 

@@ -4,6 +4,7 @@
       [-m complete_germline] [-c CPUS] [--record_statistics] [--enhanced_multiprocessing] [-v N]
       [--compress_output] [--masked_base_quality Q] [--hash_read_names] [--known_sites PANEL.vcf[.gz]]
       [--discover_sites] [--mask_sa_clips]
+      [--discover_min_base_quality Q] [--discover_min_mapq M] [--discover_exclude_flags F] [--discover_rule both|normal]
 
 samples.tsv: tumor<TAB>normal<TAB>vcf per line, paths relative to DIR, '#' lines skipped.
 Outputs next to the inputs: re.sub('.bam|.sam|.cram', '.anonymized', path) + .1/.2.fastq
@@ -48,6 +49,21 @@ run writes exactly what a run without the option writes on BAMs rewritten that w
 is the donor's germline SNV list: it is never logged or written, the log gives counts only. Limits:
 indels are not discovered; a supplementary record's bases in the primary's soft clip are not masked
 (--mask_sa_clips closes this); the pre-pass decodes every record a second time.
+--discover_min_base_quality Q (0..93, default 0), --discover_min_mapq M (0..255, default 0),
+--discover_exclude_flags F (0..65535, decimal or 0x..., default 0) and --discover_rule both|normal
+(default both) refine --discover_sites and are command-line errors without it (environment defaults:
+GANON_DISCOVER_MIN_BASE_QUALITY, GANON_DISCOVER_MIN_MAPQ, GANON_DISCOVER_EXCLUDE_FLAGS, GANON_DISCOVER_RULE).
+The first three filter the evidence, for tumor and normal alike: a base counts only when its own quality
+is at least Q (a record without qualities stores 0xFF and passes), on a record with mapq at least M and
+no flag bit of F (1024 duplicates, 512 QC failures, 256 secondary, 2048 supplementary). Rule both is the
+intersection above. Under rule normal every allele a normal read shows is a site, whatever the tumor
+shows: where the tumor lost a haplotype (loss of heterozygosity) or has no coverage the intersection is
+empty and the donor's heterozygous alleles would stay in the normal's FASTQ; the evidence that an allele
+is germline is the normal's, and the pair's own SNV positions are left out of the table anyway. Without a
+filter every sequencing error of the normal becomes a site under rule normal: give it with Q and M. The
+mask itself is not filtered: every base that shows a site's ALT is rewritten, whatever its quality or
+its record's mapq. There are no depth, read-count or strand thresholds: the tally keeps OR-ed bits, not
+counts, which is what lets records be tallied twice. The log gains the four settings and counts only.
 --mask_sa_clips (an extension; --no-mask_sa_clips; GANON_MASK_SA_CLIPS=1 is the same default): with a
 table (--known_sites, --discover_sites or both; without one the option is a command-line error) the mask
 also follows each record's SA:Z tag. A chimeric read's primary record holds the whole sequence, and the
@@ -118,12 +134,43 @@ def exec_parser(argv=None):
                         help="Mask every SNV allele that a tumor read and a normal read of the pair both show, "
                              "genome-wide: a pre-pass over both BAMs builds the pair's own site table (default: "
                              "GANON_DISCOVER_SITES)")
+    parser.add_argument("--discover_min_base_quality", type=_int_in("--discover_min_base_quality", 0, 93), metavar="Q",
+                        default=None,
+                        help="With --discover_sites: a base is evidence only when its own quality is >= Q, 0..93 "
+                             "(default: GANON_DISCOVER_MIN_BASE_QUALITY, else 0)")
+    parser.add_argument("--discover_min_mapq", type=_int_in("--discover_min_mapq", 0, 255), metavar="M", default=None,
+                        help="With --discover_sites: records with mapq < M give no evidence, 0..255 (default: "
+                             "GANON_DISCOVER_MIN_MAPQ, else 0)")
+    parser.add_argument("--discover_exclude_flags", type=_int_in("--discover_exclude_flags", 0, 65535), metavar="F",
+                        default=None,
+                        help="With --discover_sites: records with a flag bit of F give no evidence, 0..65535, decimal or "
+                             "0x... (default: GANON_DISCOVER_EXCLUDE_FLAGS, else 0)")
+    parser.add_argument("--discover_rule", type=str, choices=["both", "normal"], default=None,
+                        help="With --discover_sites: both, an allele is a site when a tumor and a normal read show it; "
+                             "normal, when a normal read shows it, whatever the tumor shows (default: GANON_DISCOVER_RULE, "
+                             "else both). The mask itself is never filtered")
     parser.add_argument("--mask_sa_clips", action=BooleanOptionalAction,
                         help="With --known_sites and / or --discover_sites: mask soft-clipped bases too, along the "
                              "alignments the record's SA tag names (default: GANON_MASK_SA_CLIPS)")
     parser.add_argument("-v", "--verbose", type=int, required=False, default=2, help="Verbosity of logging")
     parser.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     return parser.parse_args(argv)
+
+
+def _int_in(option: str, lo: int, hi: int):
+    """An argparse type: an integer lo..hi, decimal or 0x...."""
+    from argparse import ArgumentTypeError
+
+    def parse(text: str) -> int:
+        try:
+            v = int(text, 16) if text.strip().lower().startswith("0x") else int(text, 10)
+        except ValueError:
+            raise ArgumentTypeError(f"{option}: not a number: {text!r}") from None
+        if not lo <= v <= hi:
+            raise ArgumentTypeError(f"{option} is {lo}..{hi}, not {v}")
+        return v
+    parse.__name__ = "int"
+    return parse
 
 
 def join_dir_file(directory: str, param: str) -> str:
@@ -169,6 +216,26 @@ def run_anonymizer(argv=None) -> None:
     if (os.environ.get("GANON_MASK_SA_CLIPS", "0") == "1" and not os.environ.get("GANON_KNOWN_SITES")
             and os.environ.get("GANON_DISCOVER_SITES", "0") != "1"):   # (before any file is opened)
         logging.error("--mask_sa_clips needs a site table: give --known_sites PANEL.vcf[.gz], --discover_sites or both")
+        sys.exit(1)
+    for value, env in ((config.discover_min_base_quality, "GANON_DISCOVER_MIN_BASE_QUALITY"),
+                       (config.discover_min_mapq, "GANON_DISCOVER_MIN_MAPQ"),
+                       (config.discover_exclude_flags, "GANON_DISCOVER_EXCLUDE_FLAGS"),
+                       (config.discover_rule, "GANON_DISCOVER_RULE")):
+        if value is not None:
+            os.environ[env] = str(value)
+    from . import discover_sites
+    try:   # (before any file is opened: a value out of range, or a filter or rule with nothing to refine)
+        rule = discover_sites.rule_default()
+    except ValueError as e:
+        logging.error("%s", e)
+        sys.exit(1)
+    given = [o for o, v in (("--discover_min_base_quality", config.discover_min_base_quality),
+                            ("--discover_min_mapq", config.discover_min_mapq),
+                            ("--discover_exclude_flags", config.discover_exclude_flags),
+                            ("--discover_rule", config.discover_rule)) if v is not None]
+    if not discover_sites.default_on() and (given or rule != discover_sites.SiteRule()):
+        logging.error("%s needs --discover_sites: the evidence filters and the rule refine the pair's own site table",
+                      ", ".join(given) if given else "a GANON_DISCOVER_* filter or rule default")
         sys.exit(1)
     from . import native
     try:   # (a malformed key ends the run here, before any file is opened)

@@ -13,7 +13,7 @@ import os
 import threading
 import weakref
 import time
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -227,6 +227,7 @@ def hip_lib():
     lib.ganon_ctx_set_sa_clips.argtypes = [_p, C.c_int32, C.c_char_p, _i64p, _i32p]
     lib.ganon_ctx_sa_clips_counts.argtypes = [_p, _i64p, _i64p]
     lib.ganon_dtally_create.argtypes = [_p, _u8p, C.c_int64, C.POINTER(_p)]
+    lib.ganon_dtally_create_ex.argtypes = [_p, _u8p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(_p)]
     lib.ganon_site_compact_tile.argtypes = []
     lib.ganon_ctx_set_site_tally.argtypes = [_p, _p, C.c_int32, C.c_int32]
     lib.ganon_dtally_compact.argtypes = [_p, _p, C.c_void_p, _i64p]
@@ -274,7 +275,7 @@ EXPORTED_HIP_SYMBOLS = (
     "ganon_bam_walk_params", "ganon_ctx_set_name_key", "ganon_ctx_set_known_sites", "ganon_ctx_known_sites_masked",
     "ganon_ctx_set_sa_clips", "ganon_ctx_sa_clips_counts",
     "ganon_site_compact_tile", "ganon_dtally_create", "ganon_ctx_set_site_tally", "ganon_dtally_compact",
-    "ganon_dtally_sites", "ganon_dtally_free",
+    "ganon_dtally_sites", "ganon_dtally_free", "ganon_dtally_create_ex",
     "ganon_pinned_alloc", "ganon_pinned_free", "ganon_pinned_stats", "ganon_region_decode",
     "ganon_deflate_bound", "ganon_deflate_bgzf",
 )
@@ -297,6 +298,7 @@ EXPORTED_HOST_SYMBOLS = (
     "ganon_bam_reader_sa_clips_masked", "ganon_bam_reader_sa_entries_ignored",
     "ganon_site_tally_create", "ganon_site_tally_destroy", "ganon_site_tally_bytes", "ganon_site_tally_count",
     "ganon_site_tally_finish", "ganon_site_tally_release", "ganon_bam_open_ex2", "ganon_bam_reader_set_site_tally",
+    "ganon_site_tally_create_ex",
 )
 
 
@@ -371,21 +373,57 @@ def site_compact_tile() -> int:
     return int(hip_lib().ganon_site_compact_tile())
 
 
+SITE_RULE_MODES = ("both", "normal")   # csrc/ganon_site_tally.h: ganon_st::kBoth, kNormal
+
+
+class SiteRule(NamedTuple):
+    """--discover_sites: the evidence filters and the mode of a tally (csrc/ganon_site_tally.h,
+    ``ganon_st::Rule``). A base is evidence only with its own quality byte >= ``min_base_quality``
+    (0..93), on a record with mapq >= ``min_mapq`` (0..255) and no flag bit of ``exclude_flags``
+    (0..65535). ``mode`` "both": a site is an allele both datasets show; "normal": one the normal shows.
+    The default is the rule without filters."""
+    min_base_quality: int = 0
+    min_mapq: int = 0
+    exclude_flags: int = 0
+    mode: str = "both"
+
+    def checked(self) -> "SiteRule":
+        q, m, f = int(self.min_base_quality), int(self.min_mapq), int(self.exclude_flags)
+        if not 0 <= q <= 93:
+            raise ValueError(f"--discover_min_base_quality is 0..93, not {q}")
+        if not 0 <= m <= 255:
+            raise ValueError(f"--discover_min_mapq is 0..255, not {m}")
+        if not 0 <= f <= 65535:
+            raise ValueError(f"--discover_exclude_flags is 0..65535, not {f}")
+        if self.mode not in SITE_RULE_MODES:
+            raise ValueError(f"--discover_rule is one of {', '.join(SITE_RULE_MODES)}, not {self.mode!r}")
+        return SiteRule(q, m, f, self.mode)
+
+    @property
+    def filtered(self) -> bool:
+        return bool(self.min_base_quality or self.min_mapq or self.exclude_flags)
+
+    def c_args(self) -> tuple:
+        r = self.checked()
+        return r.min_base_quality, r.min_mapq, r.exclude_flags, SITE_RULE_MODES.index(r.mode)
+
+
 class DeviceTally:
     """--discover_sites: the evidence tally of one reference sequence in device memory (``ganon_dtally``,
     include/ganon.h) on a GpuInflater's context. ``ref_nt16``: the sequence's upper-cased packed bases
-    ((length + 1) // 2 bytes). ``finish(host_bytes)`` ORs in a host tally's bytes of the same sequence
-    (an address or None), compacts on the device and returns (positions int32, codes uint8); the object is
-    released with it."""
+    ((length + 1) // 2 bytes). ``rule``: a SiteRule (None: no filter, mode "both"). ``finish(host_bytes)``
+    ORs in a host tally's bytes of the same sequence (an address or None), compacts on the device under
+    the rule's mode and returns (positions int32, codes uint8); the object is released with it."""
 
-    def __init__(self, inflater: "GpuInflater", ref_nt16: np.ndarray, length: int):
+    def __init__(self, inflater: "GpuInflater", ref_nt16: np.ndarray, length: int, rule: Optional[SiteRule] = None):
         self._inf = inflater
         self._lib = inflater._lib
         ref = np.ascontiguousarray(ref_nt16, np.uint8)
         if len(ref) < (int(length) + 1) // 2:
             raise GanonError("DeviceTally: the packed reference is shorter than the sequence")
         h = _p()
-        if self._lib.ganon_dtally_create(inflater.handle, _ptr(ref, _u8p), int(length), C.byref(h)) != 0:
+        self.rule = (rule or SiteRule()).checked()
+        if self._lib.ganon_dtally_create_ex(inflater.handle, _ptr(ref, _u8p), int(length), *self.rule.c_args(), C.byref(h)) != 0:
             raise GanonError(self._lib.ganon_last_error(inflater.handle).decode(errors="replace"))
         self._h = h
         self.length = int(length)
@@ -1928,6 +1966,8 @@ def host_lib():
         f.argtypes = [_p]
         f.restype = C.c_int64
     lib.ganon_site_tally_create.argtypes = [C.c_int32, _u8p, _i64p, _i64p, C.POINTER(_p)]
+    lib.ganon_site_tally_create_ex.argtypes = [C.c_int32, _u8p, _i64p, _i64p, C.c_int32, C.c_int32, C.c_uint32, C.c_int32,
+                                               C.POINTER(_p)]
     lib.ganon_site_tally_destroy.argtypes = [_p]
     lib.ganon_site_tally_destroy.restype = None
     lib.ganon_site_tally_bytes.argtypes = [_p, C.c_int32]

@@ -507,10 +507,18 @@ GANON_API int ganon_ctx_sa_clips_counts(ganon_ctx *ctx, int64_t *masked, int64_t
  * sites in position order in device memory (k_site_compact), *n their number; the tally bytes are
  * never downloaded. ganon_dtally_sites copies the n positions and codes (ref_nt16 << 4 | alt) to the
  * host. ganon_dtally_free releases everything (and clears the context's tally if it is this one).
- * ganon_site_compact_tile: the positions one workgroup of k_site_compact takes. */
+ * ganon_site_compact_tile: the positions one workgroup of k_site_compact takes.
+ * ganon_dtally_create_ex (additive): the tally with the rule of ganon_site_tally_create_ex
+ * (min_base_quality 0..93, min_mapq 0..255, exclude_flags 0..65535, mode 0 both / 1 normal). With an
+ * evidence filter set k_bam_site_tally runs as its filtered instantiation (same kernel name), which
+ * also reads the mapq column and, at mismatches, the quality bytes; with none it is the kernel
+ * ganon_dtally_create's tally runs. Under mode 1 ganon_dtally_compact takes alt = the high nibble alone,
+ * after the same OR with host_bytes. ganon_dtally_create is the _ex call with the zero rule. */
 typedef struct ganon_dtally ganon_dtally;
 GANON_API int ganon_site_compact_tile(void);
 GANON_API int ganon_dtally_create(ganon_ctx *ctx, const uint8_t *ref_nt16, int64_t len, ganon_dtally **out);
+GANON_API int ganon_dtally_create_ex(ganon_ctx *ctx, const uint8_t *ref_nt16, int64_t len, int32_t min_base_quality,
+                                     int32_t min_mapq, uint32_t exclude_flags, int32_t mode, ganon_dtally **out);
 GANON_API int ganon_ctx_set_site_tally(ganon_ctx *ctx, ganon_dtally *tally, int32_t dataset, int32_t tid);
 GANON_API int ganon_dtally_compact(ganon_ctx *ctx, ganon_dtally *tally, const uint8_t *host_bytes, int64_t *n);
 GANON_API int ganon_dtally_sites(ganon_ctx *ctx, ganon_dtally *tally, int32_t *pos, uint8_t *code);

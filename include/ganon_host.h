@@ -126,10 +126,20 @@ GANON_HOST_API int64_t ganon_bam_sa_entries_ignored(const ganon_bam *bam);
  * ganon_site_tally_bytes: the sequence's byte array (NULL: no evidence yet), for a device compaction
  * that ORs it in (include/ganon.h) — then ganon_site_tally_release frees it. ganon_site_tally_count:
  * the sites of a sequence now. ganon_site_tally_finish: writes them in position order (at most cap;
- * -1 with an error when they are more) and frees the bytes; returns their number. */
+ * -1 with an error when they are more) and frees the bytes; returns their number.
+ * ganon_site_tally_create_ex (additive): the tally with a rule, which every reader it is set on and
+ * count / finish read from it. Evidence filters: a base is evidence only when its own quality byte,
+ * compared unsigned, is >= min_base_quality (0..93; a record without qualities stores 0xFF and passes);
+ * a record with mapq < min_mapq (0..255) or flag & exclude_flags (0..65535) non-zero gives none. They
+ * filter evidence only, for both datasets alike. mode 0 (both): a site is low & high as above; mode 1
+ * (normal): position r is a site when the high nibble is non-zero, its code ref_nt16 << 4 | high, the
+ * low nibble is not consulted. ganon_site_tally_create is the _ex call with the zero rule. */
 typedef struct ganon_site_tally ganon_site_tally;
 GANON_HOST_API int ganon_site_tally_create(int32_t n_seq, const uint8_t *nt16, const int64_t *nib_off, const int64_t *len,
                                            ganon_site_tally **out);
+GANON_HOST_API int ganon_site_tally_create_ex(int32_t n_seq, const uint8_t *nt16, const int64_t *nib_off, const int64_t *len,
+                                              int32_t min_base_quality, int32_t min_mapq, uint32_t exclude_flags, int32_t mode,
+                                              ganon_site_tally **out);
 GANON_HOST_API void ganon_site_tally_destroy(ganon_site_tally *tally);
 GANON_HOST_API const uint8_t *ganon_site_tally_bytes(const ganon_site_tally *tally, int32_t seq);
 GANON_HOST_API int64_t ganon_site_tally_count(const ganon_site_tally *tally, int32_t seq);

@@ -28,7 +28,14 @@ clip bases rewritten and the entries ignored on both sides.
 sequence most records lie on, as the tumor dataset — k_bam_site_tally joins the kernel list —, the host
 decoder tallying inside its column pass; the line reports the positions with evidence on both sides (they
 must agree), k_site_compact over that sequence and over a synthetic 20 Mb sequence whose bytes come up
-from the host (one position in a thousand a site).
+from the host (one position in a thousand a site), under both modes of --discover_rule.
+
+--min_base_quality Q, --min_mapq M, --exclude_flags F, --rule both|normal (with --site_tally): the tally on
+both sides carries that rule (--discover_min_base_quality, --discover_min_mapq, --discover_exclude_flags,
+--discover_rule). With an evidence filter set k_bam_site_tally runs as its filtered instantiation, and the
+records are given mapqs 0, 20, 40 and 60 in equal shares and the duplicate flag on one in twenty (the
+generator's base qualities are uniform in 2..40 already), so that every filter passes and drops records;
+without one the stream is the plain one, and the kernel is the one a tally without a rule runs.
 """
 import argparse
 import json
@@ -99,7 +106,22 @@ def with_sa_clips(recs: bytes, frac: float, ref_names, ref_lens, seed: int = 3):
     return b"".join(out), changed
 
 
-def compact_20mb(g, n: int = 20_000_000, seed: int = 2) -> dict:
+def with_mapqs_and_duplicates(recs: bytes, seed: int = 5) -> bytes:
+    """``recs`` (BAM records back to back) with mapq 0, 20, 40 or 60 at random and flag 0x400 on one record in
+    twenty."""
+    import struct
+    rng = np.random.default_rng(seed)
+    out, p, n = bytearray(recs), 0, len(recs)
+    while p < n:
+        bs = struct.unpack_from("<i", out, p)[0]
+        out[p + 4 + 9] = int(rng.integers(0, 4)) * 20
+        if rng.random() < 0.05:
+            struct.pack_into("<H", out, p + 4 + 14, struct.unpack_from("<H", out, p + 4 + 14)[0] | 0x400)
+        p += 4 + bs
+    return bytes(out)
+
+
+def compact_20mb(g, n: int = 20_000_000, seed: int = 2, mode: str = "both") -> dict:
     """k_site_compact on a synthetic ``n``-base sequence: the evidence bytes uploaded as a host tally's."""
     from genomeanonymizer_amd import native
     rng = np.random.default_rng(seed)
@@ -110,17 +132,20 @@ def compact_20mb(g, n: int = 20_000_000, seed: int = 2) -> dict:
     alt = (np.uint8(1) << ((ref[at] + 1) % 4)).astype(np.uint8)
     host[at] = alt | (alt << 4)
     host[rng.choice(n, n // 100, replace=False)] |= 0x10      # evidence on one side alone
-    dt = native.DeviceTally(g, packed, n)
+    dt = native.DeviceTally(g, packed, n, native.SiteRule(mode=mode))
     pos, code = dt.finish(host.ctypes.data)
-    per = dict(g.kernel_times())
-    exp = np.nonzero(host & (host >> 4) & 15)[0]
-    return {"bases": n, "sites": int(len(pos)), "kernels_ms": {k: round(v, 3) for k, v in per.items()},
-            "equals_numpy": bool(np.array_equal(pos, exp) and np.array_equal(code & 15, (host & (host >> 4) & 15)[exp])
+    per: dict = {}
+    for k, v in g.kernel_times():
+        per[k] = per.get(k, 0.0) + v
+    alt = ((host if mode == "both" else 15) & (host >> 4) & 15).astype(np.uint8)
+    exp = np.nonzero(alt)[0]
+    return {"bases": n, "rule": mode, "sites": int(len(pos)), "kernels_ms": {k: round(v, 3) for k, v in per.items()},
+            "equals_numpy": bool(np.array_equal(pos, exp) and np.array_equal(code & 15, alt[exp])
                                  and np.array_equal(code >> 4, np.uint8(1) << ref[exp]))}
 
 
 def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = None, sites_per_kb: float = 0.0,
-            site_tally: bool = False, sa_clips: float = 0.0) -> dict:
+            site_tally: bool = False, sa_clips: float = 0.0, rule=None) -> dict:
     import gzip
     from genomeanonymizer_amd import native
     from genomeanonymizer_amd.io.bam import ReadTable
@@ -140,6 +165,8 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
             hdr = BamReader(paths["T"], 1)
             recs, n_clipped = with_sa_clips(recs, sa_clips, hdr.ref_names, hdr.ref_lens)
             hdr.close()
+        if site_tally and rule is not None and rule.filtered:
+            recs = with_mapqs_and_duplicates(recs)
         tiles = max(1, (mb << 20) // max(1, len(recs)))
         stream = np.frombuffer(head + recs * tiles, np.uint8)
         g = native.GpuInflater(0, min_blocks=1)
@@ -163,12 +190,12 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
             from genomeanonymizer_amd.io.bam import BamReader
             from genomeanonymizer_amd.io.fasta import FastaRef
             hdr = BamReader(paths["T"], 1)
-            tally = HostTally.of_fasta(FastaRef(paths["ref"]))
+            tally = HostTally.of_fasta(FastaRef(paths["ref"]), rule)
             seq_of = tally.seq_of_tid(hdr.ref_names)
             hdr.close()
             tally_tid = int(np.frombuffer(recs[4:8], np.int32)[0])   # (the first record's sequence)
             seq = int(seq_of[tally_tid])
-            dtally = native.DeviceTally(g, tally.reference_of(seq), int(tally.lengths[seq]))
+            dtally = native.DeviceTally(g, tally.reference_of(seq), int(tally.lengths[seq]), rule)
             g.set_site_tally(dtally, 0, tally_tid)
         runs = []
         cols, _ = native.bam_columns_device(g.handle, stream, p, len(stream), on_host=True)   # (warm: blocks cached)
@@ -191,8 +218,13 @@ def measure(mb: int = 256, threads: int = 16, reps: int = 3, name_key: bytes = N
             g.set_site_tally(dtally, 1, tally_tid)
             native.bam_columns_device(g.handle, stream, p, len(stream), on_host=True)
             dpos, dcode = dtally.finish()
+            per_c: dict = {}
+            for k, v in g.kernel_times():
+                per_c[k] = per_c.get(k, 0.0) + v
             tally_out = {"tid": tally_tid, "sequence_bases": int(tally.lengths[seq]), "positions_with_evidence_device": int(len(dpos)),
-                         "compact_kernels_ms": {k: round(v, 3) for k, v in g.kernel_times()}, "compact_20Mb": compact_20mb(g)}
+                         "rule": None if rule is None else dict(rule._asdict()),
+                         "compact_kernels_ms": {k: round(v, 3) for k, v in per_c.items()}, "compact_20Mb": compact_20mb(g),
+                         "compact_20Mb_normal": compact_20mb(g, mode="normal")}
         g.close()
         best = min(runs, key=lambda x: x[0])
         nr = len(cols["pos"])
@@ -256,13 +288,23 @@ def main() -> None:
                          "the decoders mask the clips along it (--mask_sa_clips)")
     ap.add_argument("--site_tally", action="store_true",
                     help="decode with an evidence tally (--discover_sites) on both sides, and time k_site_compact")
+    ap.add_argument("--min_base_quality", type=int, default=0, metavar="Q", help="with --site_tally: the rule's base quality")
+    ap.add_argument("--min_mapq", type=int, default=0, metavar="M", help="with --site_tally: the rule's mapq")
+    ap.add_argument("--exclude_flags", type=lambda t: int(t, 0), default=0, metavar="F", help="with --site_tally: excluded flags")
+    ap.add_argument("--rule", choices=["both", "normal"], default="both", help="with --site_tally: --discover_rule")
     args = ap.parse_args()
     key = None
     if args.hash_names:
         from genomeanonymizer_amd import native
         v = os.environ.get(native.NAME_KEY_ENV)
         key = native.parse_name_key(v) if v is not None else BENCH_KEY
-    print(json.dumps(measure(args.mb, args.threads, args.reps, key, args.known_sites, args.site_tally, args.sa_clips)))
+    rule = None
+    if args.site_tally:
+        from genomeanonymizer_amd import native
+        rule = native.SiteRule(args.min_base_quality, args.min_mapq, args.exclude_flags, args.rule).checked()
+    elif args.min_base_quality or args.min_mapq or args.exclude_flags or args.rule != "both":
+        raise SystemExit("--min_base_quality, --min_mapq, --exclude_flags and --rule need --site_tally")
+    print(json.dumps(measure(args.mb, args.threads, args.reps, key, args.known_sites, args.site_tally, args.sa_clips, rule)))
 
 
 if __name__ == "__main__":

@@ -299,12 +299,24 @@ int host_copy(ganon_ctx *ctx, const ganon_dbatch *db, HostCopy &h) {
 // Plan a batch whose raw arrays are on the device (ganon_prep::plan: validation, prep mode, sizes),
 // the huge-scope tiles (from `host`, or host copies), and upload the group kernels' aux pointers
 // and the static totals (async).
+// The fused mode's buffers in the host copy of the aux pointers (every plan may grow them).
+void set_fused_aux(ganon_dbatch *db) {
+  GrpAux &a = db->aux_h;
+  a.desc = static_cast<const int4 *>(db->b_desc.p);
+  a.sdirty = static_cast<const uint8_t *>(db->b_sdirty.p);
+  a.xrec = static_cast<const int4 *>(db->b_xrec.p);
+  a.xidx = static_cast<const int32_t *>(db->b_xidx.p);
+  a.xlist = static_cast<int2 *>(db->b_xlist.p);
+}
+
 int prepare(ganon_ctx *ctx, ganon_dbatch *db, const ganon_batch *host, bool allow_spec = false) {
   int rc;
   if ((rc = ganon_prep::plan(ctx, db, allow_spec))) return rc;   // (it clears the step's flags first)
   if (db->spec && !db->spec_sized) {
     // the previous plan's tiles (none), aux pointers and static totals, unchanged on the host; copied
-    // again (a reload clears the device's small state)
+    // again (a reload clears the device's small state) — but for the fused mode's buffers, which the
+    // plan may have grown (another GANON_PARAM_XREC_INIT since the previous plan)
+    set_fused_aux(db);
     HIP_OR_FAIL(hipMemcpyAsync(db->aux, &db->aux_h, sizeof db->aux_h, hipMemcpyHostToDevice, ctx->stream));
     HIP_OR_FAIL(hipMemcpyAsync(db->static_totals, db->static_h, GANON_N_TOTALS * sizeof(unsigned long long),
                                hipMemcpyHostToDevice, ctx->stream));
@@ -332,15 +344,11 @@ int prepare(ganon_ctx *ctx, ganon_dbatch *db, const ganon_batch *host, bool allo
   a.incid_read = db->B.incid_read;
   a.ref_start = db->B.ref_start;
   a.read_end = db->B.read_end;
-  a.desc = static_cast<const int4 *>(db->b_desc.p);
   a.incid_off = db->B.incid_off;
   a.ref_off = db->B.ref_off;
-  a.sdirty = static_cast<const uint8_t *>(db->b_sdirty.p);
   a.inc4 = static_cast<const int4 *>(db->b_inc4.p);
   a.rrec = static_cast<const int4 *>(db->b_rrec.p);
-  a.xrec = static_cast<const int4 *>(db->b_xrec.p);
-  a.xidx = static_cast<const int32_t *>(db->b_xidx.p);
-  a.xlist = static_cast<int2 *>(db->b_xlist.p);
+  set_fused_aux(db);
   a.n_reads = db->n_reads;
   a.err = db->err;
   a.ws_part = static_cast<unsigned long long *>(db->b_wspart.p);

@@ -225,6 +225,9 @@ __device__ __forceinline__ void block_parts(unsigned long long (&acc)[kParts], u
 // chain of dependent loads for one thread): the reference length (bam_endpos), the aligned
 // segments as walk_segments cuts them (per-lane query offsets from a wave prefix sum, the
 // read-length clip), the I/D ops; bad_op = the first op code above 8 (the walk stops there), or -1.
+// Query-consuming lengths may sum past 2^31 (each op holds up to 2^28 - 1): every per-lane query delta
+// is capped at the read length L (below 2^24: the scan's check) and the carried offset stops at L, as
+// walk_segments stops there — an offset that wrapped counted segments walk_segments never writes.
 struct CigarWalk {
   long long rl;
   int ns, nid, bad_op;
@@ -247,13 +250,13 @@ __device__ __forceinline__ CigarWalk wave_cigar_walk(const uint32_t *__restrict_
       break;
     }
     const bool al = is_aligned_op(op);
-    const int dq = (al || op == 1 || op == 4) ? len : 0;
+    const int dq = (al || op == 1 || op == 4) ? min(len, L) : 0;
     const int incl = ganon_wave::incl_sum(dq);
     const int q0 = q + incl - dq;
     seg += (al && q0 < L) ? (min(len, L - q0) + kSegMaxLen - 1) / kSegMaxLen : 0;
     id += (op == 1 || op == 2) ? 1 : 0;
     dr += (al || op == 2 || op == 3) ? (long long)len : 0ll;
-    q += ganon_wave::last(incl);
+    q = min(q + ganon_wave::last(incl), L);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -318,7 +321,7 @@ __global__ void __launch_bounds__(kPrepThreads, GANON_SCAN_BLOCKS) k_prep_scan(c
           else if (nc[u] < 0 || co64[u] < 0 || co64[u] + nc[u] > R.n_cigar_ops) { report(err, kErrReadCigar, r); ok[u] = false; }
           if (ds[u] > 1) report(err, kErrReadDataset, r);
           if (ws[u] < -1 || ws[u] >= R.n_scopes) { report(err, kErrReadWriteScope, r, ws[u]); ok[u] = false; }
-          if (L[u] >= (1 << 24)) report(err, kErrReadLong, r);
+          if (L[u] >= (1 << 24)) { report(err, kErrReadLong, r); ok[u] = false; }   // (the walks rely on L < 2^24)
         }
         co[u] = ok[u] ? (Off)co64[u] : (Off)0;   // (checked: in range)
         so[u] = ok[u] ? (Off)so64[u] : (Off)0;
@@ -359,7 +362,10 @@ __global__ void __launch_bounds__(kPrepThreads, GANON_SCAN_BLOCKS) k_prep_scan(c
           continue;
         }
         // one walk: reference length (bam_endpos), aligned segments as walk_segments cuts them,
-        // I/D ops (the indel tally's observations); the first segment for the descriptor
+        // I/D ops (the indel tally's observations); the first segment for the descriptor. The query
+        // offset stops advancing at the read length, as walk_segments stops there: lengths that sum
+        // past 2^31 wrapped it, and the wrapped offset counted (and described) segments that
+        // walk_segments never writes
         int64_t rl = 0;
         int q = 0, ns = 0, nid = 0;
         int fq = 0, fn = 0;
@@ -378,11 +384,11 @@ __global__ void __launch_bounds__(kPrepThreads, GANON_SCAN_BLOCKS) k_prep_scan(c
                 fn = min(min(len, L[u] - q), kSegMaxLen);
               }
               ns += (min(len, L[u] - q) + kSegMaxLen - 1) / kSegMaxLen;
+              q += len;
             }
-            q += len;
             rl += len;
           } else if (op == 1 || op == 4) {
-            q += len;
+            q = q < L[u] ? q + len : q;
           } else if (op == 2 || op == 3) {
             rl += len;
           }
@@ -1368,7 +1374,9 @@ __global__ void __launch_bounds__(kPrepThreads) k_prep_read_recs(const Raw R, co
       const uint32_t w = k < nc ? R.cigar[co + k] : 0u;
       const int op = (int)(w & 0xF), len = (int)(w >> 4);
       const bool al = is_aligned_op(op);
-      const int dq = (al || op == 1 || op == 4) ? len : 0;
+      // (query deltas capped at L < 2^24: 64 of them cannot wrap the prefix sum, and an op at or past
+      // L gives nothing either way; the reference deltas sum to at most INT32_MAX: the scan's check)
+      const int dq = (al || op == 1 || op == 4) ? min(len, L) : 0;
       const int dp = (al || op == 2 || op == 3) ? len : 0;
       const int iq = ganon_wave::incl_sum(dq), ip = ganon_wave::incl_sum(dp);
       const int q0 = q + iq - dq, p0 = p + ip - dp;
@@ -1853,10 +1861,13 @@ int plan(ganon_ctx *ctx, ganon_dbatch *db, bool allow_spec) {
   int32_t *xidx = nullptr;
   uint8_t *sdirty = nullptr;   // (k_prep_cands)
   if (db->fused) {
-    // extras records of multi-segment reads: the list keeps its capacity (at least one per 8 reads)
+    // extras records of multi-segment reads: the list keeps its capacity (at least one per 8 reads).
+    // With GANON_PARAM_XREC_INIT the capacity asked for stays until a full plan regrows it: the second
+    // plan used to take the default, and a speculative replan of the same sizes, which reuses the
+    // previous plan's aux pointers (prepare), left the group kernel reading the freed list
     const int64_t xwant = std::min<int64_t>(
-        INT32_MAX, ctx->xrec_init > 0 && db->xcap == 0 ? (int64_t)ctx->xrec_init
-                                                       : std::max<int64_t>({db->xcap, int64_t(65536), nr / 8}));
+        INT32_MAX, ctx->xrec_init > 0 ? std::max<int64_t>(db->xcap, (int64_t)ctx->xrec_init)
+                                      : std::max<int64_t>({db->xcap, int64_t(65536), nr / 8}));
     if ((rc = grow_n(ctx, db->b_desc, (size_t)std::max<int64_t>(nr, 1), &desc)) ||
         (rc = grow_n(ctx, db->b_cand, 2 * (size_t)g_bound, &cand)) ||
         (rc = grow_n(ctx, db->b_sdirty, (size_t)std::max<int64_t>(ns, 1), &sdirty)) ||
@@ -1865,7 +1876,9 @@ int plan(ganon_ctx *ctx, ganon_dbatch *db, bool allow_spec) {
         (rc = grow_n(ctx, db->b_xidx, (size_t)std::max<int64_t>(nr, 1), &xidx)))
       return rc;
     db->xcap = std::min<int64_t>(INT32_MAX, (int64_t)((db->b_xrec.bytes - 128) / sizeof(int4)));
-    if (ctx->xrec_init > 0 && db->xcap > xwant) db->xcap = xwant;   // (testing knob: the capacity asked for)
+    // (testing knob: the allocation's rounding does not count. A capacity the batch already has wins
+    // over a smaller GANON_PARAM_XREC_INIT set later: the knob sizes a fresh upload's first list)
+    if (ctx->xrec_init > 0 && db->xcap > xwant) db->xcap = xwant;
   }
   db->cand = cand;
   unsigned int *long_count = db->long_count;

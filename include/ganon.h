@@ -238,8 +238,10 @@ typedef struct ganon_kernel_time {
 } ganon_kernel_time;
 GANON_API int ganon_last_kernel_times(ganon_ctx *ctx, ganon_kernel_time *out, int max_k);
 
-/* Plan of an uploaded batch: [scope groups, segment records, huge scopes (> 2^20 positions, tile
- * path), huge-scope tiles, far-mask capacity (nibbles), reads written by huge scopes, overflow-region
+/* Plan of an uploaded batch: [scope groups (workgroups of the group kernel: in the one-segment modes
+ * the closed-form bound (incidences + weight (scopes - 1)) / target + 1 the run is launched for — the
+ * blocks past the scan's group count exit at once — else the groups cut), segment records, huge
+ * scopes (> 2^20 positions, tile path), huge-scope tiles, far-mask capacity (nibbles), reads written by huge scopes, overflow-region
  * entries, written reads]. */
 GANON_API int ganon_batch_info(ganon_dbatch *db, int64_t *info8);
 /* Shape of the planned batch, from the device scan: [I/D CIGAR ops (0: the indel tally has nothing

@@ -481,11 +481,11 @@ def test_hip_empty_and_degenerate_batches(masker):
     bad = dict(arr)
     bad["write_scope"] = arr["write_scope"].copy()
     bad["write_scope"][0] = len(arr["scope_span_len"]) + 5
-    with pytest.raises(native.GanonError):
+    with pytest.raises(native.GanonError, match=r"read 0: write_scope %d out of range" % (len(arr["scope_span_len"]) + 5)):
         masker.mask(bad)
     bad = dict(arr)
     bad["scope_span_len"] = np.maximum(arr["scope_span_len"] - 10, 0).astype(np.int32)
-    with pytest.raises(native.GanonError):
+    with pytest.raises(native.GanonError, match=r"scope \d+: read \d+ outside its span"):
         masker.mask(bad)
 
 
@@ -748,7 +748,16 @@ def _two_segment_copy(arr: dict, r: int) -> dict:
 NINE_SEG = [(16, 0), (1, 1)] * 8 + [(14, 0)]
 
 
-def test_speculative_plan_of_new_counts(hip_built):
+def _assert_wants_equal_oracle(oracle, batches, wants):
+    """The expected results the speculative-plan tests take from ``mask()`` are the CPU oracle's."""
+    for x, want in zip(batches, wants):
+        o = oracle.mask(x)
+        assert _all_reads_equal(x, want[0], o[0]) == []
+        assert np.array_equal(want[1], o[1]) and np.array_equal(want[2], o[2])
+        assert want[3][0] == o[3][0] and want[3][1] == o[3][1]
+
+
+def test_speculative_plan_of_new_counts(hip_built, oracle):
     """Batches of other read / scope / incidence counts than the context's last plan speculate too
     (buffers sized from their counts, the context's last shape assumed, the scan gating the run):
     two resident batches of one sample replanned in turn give exactly their full plans' results; a
@@ -767,6 +776,7 @@ def test_speculative_plan_of_new_counts(hip_built):
     m = native.HipMasker(0)
     try:
         want = [m.mask(x) for x in (a, b, c, c2)]
+        _assert_wants_equal_oracle(oracle, (a, b, c, c2), want)
         ref = m.upload_reference(a["ref_nt16"])
         dbs = [m.upload({k: v for k, v in x.items() if k != "ref_nt16"}, ref=ref) for x in (a, b, c, c2)]
         assert dbs[3].shape()["prep_mode"] == "multi_segment_fused"
@@ -801,7 +811,7 @@ def test_speculative_plan_of_new_counts(hip_built):
         m.close()
 
 
-def test_speculative_replan_and_fallback(hip_built):
+def test_speculative_replan_and_fallback(hip_built, oracle):
     """A replan after a one-segment plan of the same sizes is speculative (no synchronization); the
     scan's reduction gates the run. A batch that does not fit (a read with two segments) or fails
     validation runs nothing; ganon_batch_download plans it in full and runs it again, or returns the
@@ -819,6 +829,7 @@ def test_speculative_replan_and_fallback(hip_built):
     m = native.HipMasker(0)
     try:
         want_a, want_b, want_b2 = m.mask(a), m.mask(b), m.mask(b2)
+        _assert_wants_equal_oracle(oracle, (a, b, b2), (want_a, want_b, want_b2))
         m.set_param(native.PARAM_SPEC_PLAN, 2)
         db = m.upload(a)
         try:
